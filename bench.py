@@ -1,13 +1,16 @@
 """bench.py — rays/sec of the ThermoNeRF rendering hot path on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     (N > 1: launched by `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...`)
 
 Default workload = the configuration BASELINE.json's `metric` is quoted on: a synthetic 800x800 RGB+thermal scene at
 192 samples/ray, exact fp32.  A *step* is one pass of the hot path over one frame (640 000 rays, forward-only, eval mode:
 proposal sampling 256+96 -> hash-grid+MLP field at S samples/ray -> alpha-composited RGB + thermal + depths), rendered
 with eval_num_rays_per_chunk = the frame (one proposal + one field launch per frame).  Rays and weights are resident in
-HBM before the timed region.  On rank 0 at N = 1 the line also carries, under `variants`, BASELINE config 2 (S = 64), the
+HBM before the timed region.  A plain run sets up, warms up, times the K steps and prints the line; everything below that
+the line carries beyond `value` and its roofline (the CPU baseline, parity, `variants`) is measured with --full only.
+--dump-outputs DIR writes the frame of the last timed step, one DIR/<output>.npy per output (float32), for comparing two builds.
+With --full, on rank 0 at N = 1 the line also carries, under `variants`, BASELINE config 2 (S = 64), the
 reference config's chunking (eval_num_rays_per_chunk = 65 536, REF config_thermal_nerf.py:30), the opt-in split-precision
 (bf16x6, f16x3) and early-termination forms, BASELINE config 4 end to end (the reference's 96-pose 1080p camera path), a
 single-GPU proxy of strong scaling over ray shards, BASELINE config 3 as the reference defines it (30 000 consecutive Trainer
@@ -15,15 +18,16 @@ iterations on fresh batches, held-out PSNR / thermal MAE, parity on the trained 
 S = 48 and S = 192 — each its own measurement, none of them `value`.
 
 N ranks (--shard weak, default): every rank renders its own frame (view = rank; rays shard with no data-path dependency)
-and the rendered pixels (36 B/ray) are all-gathered over RCCL inside the timed region, asynchronously.
+and the rendered pixels (36 B/ray) are all-gathered over RCCL inside the timed region, asynchronously; with --full the same
+ranks also time two strong-scaling frames.
 --shard frame (BASELINE config 4): ONE 1920x1080 frame, ray-sharded on the reference's chunk boundaries over the N ranks
 and all-gathered, every step; `value` = frame rays / frame latency, `scaling` = "strong".
 
 The JSON line also carries
   roofline      the dominant kernel's achieved rate (HIP events on the launch stream inside the timed region) against its
                 bound: fp32 MFMA flops for the exact-fp32 field kernel, with the HBM view alongside
-  cpu_baseline  the CPU oracle (torch fp32 restatement of the reference path) timed on a bounded sample of the same rays
-                on this box's host cores: best torch pool size AND one thread, CPU model stated (rank 0, N = 1 only)
+  cpu_baseline  (--full) the CPU oracle (torch fp32 restatement of the reference path) timed on a bounded sample of the same
+                rays on the host's cores: best torch pool size AND one thread, CPU model stated (rank 0, N = 1 only)
 """
 from __future__ import annotations
 
@@ -48,6 +52,31 @@ P0, P1 = 256, 96
 TORCH_ADAM = False  # --torch-adam: the training variants with torch.optim.Adam(fused=True) and a joined scatter (A/B of round 6's HipAdam + deferred table update)
 ATOMIC_SCATTER = False  # --atomic-scatter: config.bucketed_table_scatter = False in the train-step variants (A/B)
 REF_CHUNK = 1 << 16  # REF thermo_nerf/thermal_nerf/config_thermal_nerf.py:30
+
+
+DUMP_LIMIT_BYTES = 64 << 20  # --dump-outputs: at most this much in all
+
+
+def dump_outputs(dirname: str, out: dict, limit: int = DUMP_LIMIT_BYTES) -> None:
+    """--dump-outputs: the [n, C] output arrays of a frame as DIR/<name>.npy, float32.  A frame larger than `limit` bytes is
+    written for a fixed sample of its rays (seeded, sorted, the same at every run of the same shape) and the sample's ray
+    numbers go beside it as ray_index.npy (float64: exact for any frame)."""
+    import numpy as np
+
+    os.makedirs(dirname, exist_ok=True)
+    n = next(iter(out.values())).shape[0]
+    floats_per_ray = sum(v.shape[1] if v.dim() > 1 else 1 for v in out.values())
+    idx = None
+    if 4 * n * floats_per_ray > limit:
+        keep = ((limit - 128 * (len(out) + 1)) // (4 * floats_per_ray + 8)) & ~63  # (128 B: an .npy header)
+        g = torch.Generator().manual_seed(0)
+        idx = torch.randperm(n, generator=g)[:keep].sort().values
+        np.save(os.path.join(dirname, "ray_index.npy"), idx.numpy().astype(np.float64))
+    for k, v in out.items():
+        v = v.detach()
+        if idx is not None:
+            v = v[idx.to(v.device)]
+        np.save(os.path.join(dirname, k + ".npy"), v.float().cpu().numpy())
 
 
 def algorithmic_bytes_per_ray(S: int):
@@ -105,7 +134,18 @@ def parse():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-variants", action="store_true", help="skip the secondary measurements (profiling runs)")
     ap.add_argument("--cpu-rays", type=int, default=4096, help="rays per CPU-baseline repeat")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline figure: the CPU baseline and the parity against the CPU oracle, "
+                         "the variants (other precisions, sample counts, chunkings, the camera path, config 3, training steps) and, "
+                         "at N > 1, the strong-scaling frames.  Off (default): set up, warm up, time the steps, print the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the outputs of the last one as DIR/<name>.npy (float32; a fixed sample of "
+                         "rays if the frame exceeds %d MB).  The render path of --shard weak only" % (DUMP_LIMIT_BYTES >> 20))
     a = ap.parse_args()
+    if a.dump_outputs and (a.mode != "render" or a.shard != "weak"):
+        ap.error("--dump-outputs: the render path of --shard weak only")
+    if not a.full:  # the secondary measurements' own switches: a plain run makes none of them
+        a.no_cpu_baseline = a.no_variants = True
     global ATOMIC_SCATTER, TORCH_ADAM
     ATOMIC_SCATTER = bool(a.atomic_scatter)
     TORCH_ADAM = bool(a.torch_adam)
@@ -1079,6 +1119,8 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:  # (before any variant renders into `out`)
+        dump_outputs(args.dump_outputs, out)
     info = rccl_info(dist, world, dev)
     strong = {}
     if world > 1 and not args.no_variants:

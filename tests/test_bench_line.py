@@ -140,3 +140,38 @@ def test_emit_prints_the_detail_first_and_the_compact_line_last(full, tmp_path, 
     assert last == bench.compact_line(full)
     for d in (tmp_path, tmp_path / "gpurun_out"):
         assert strict(open(d / "bench_detail.json").read())["value"] == full["value"]
+
+
+def test_plain_run_defers_the_secondary_measurements_to_full(monkeypatch):
+    monkeypatch.setattr("sys.argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert not a.full and a.no_cpu_baseline and a.no_variants and a.dump_outputs is None and a.steps == 7
+    monkeypatch.setattr("sys.argv", ["bench.py", "--full"])
+    a = bench.parse()
+    assert a.full and not a.no_cpu_baseline and not a.no_variants
+    monkeypatch.setattr("sys.argv", ["bench.py", "--mode", "train", "--dump-outputs", "x"])
+    with pytest.raises(SystemExit):
+        bench.parse()
+
+
+def test_dump_outputs_writes_float32_arrays_within_the_limit(tmp_path):
+    import numpy as np
+    import torch
+
+    g = torch.Generator().manual_seed(1)
+    out = {"rgb": torch.rand(5000, 3, generator=g), "thermal": torch.rand(5000, 1, generator=g)}
+    bench.dump_outputs(str(tmp_path / "whole"), out)
+    for k, v in out.items():
+        got = np.load(tmp_path / "whole" / (k + ".npy"))
+        assert got.dtype == np.float32 and np.array_equal(got, v.numpy())
+    assert not (tmp_path / "whole" / "ray_index.npy").exists()
+    # over the limit: the same seeded sample of rays at every call, the sample's ray numbers beside it
+    for tag in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / tag), out, limit=20000)
+        assert sum(p.stat().st_size for p in (tmp_path / tag).iterdir()) <= 20000
+    idx = np.load(tmp_path / "a" / "ray_index.npy")
+    assert idx.dtype == np.float64 and len(idx) > 0 and np.all(np.diff(idx) > 0)
+    assert np.array_equal(idx, np.load(tmp_path / "b" / "ray_index.npy"))
+    for k, v in out.items():
+        got = np.load(tmp_path / "a" / (k + ".npy"))
+        assert got.dtype == np.float32 and np.array_equal(got, v.numpy()[idx.astype(np.int64)])

@@ -568,7 +568,7 @@ def test_config5_training_replicas_do_not_interact():
 
 
 def test_bench_two_ranks_prints_one_parseable_line():
-    """`bench.py --gpus 2` exactly as the driver launches it (torch.distributed.run, one process per rank), on the gloo backend with
+    """`bench.py --gpus 2 --full` as the driver launches it (torch.distributed.run, one process per rank), on the gloo backend with
     both ranks on this box's one GPU (RCCL refuses two ranks per device; TN_BENCH_BACKEND is bench.py's switch for that): the LAST
     stdout line is the compact record — strict JSON below the limit — with the weak-scaling value, both strong-scaling frames
     (BASELINE config 4's 1080p x S=48 and the metric's 800x800 x S=192) and the transport record."""
@@ -580,7 +580,7 @@ def test_bench_two_ranks_prints_one_parseable_line():
     env = dict(os.environ, TN_BENCH_BACKEND="gloo", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--no-cpu-baseline"]
+           "--no-cpu-baseline", "--full"]
     r = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
@@ -630,3 +630,48 @@ def test_bench_starts_its_own_ranks_when_no_launcher_did():
     bad = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "8", "--steps", "1", "--warmup", "0"], cwd=root,
                          env=dict(env, WORLD_SIZE="2", RANK="0", LOCAL_RANK="0"), capture_output=True, text=True, timeout=300)
     assert bad.returncode != 0 and "contradicts" in (bad.stderr + bad.stdout)
+
+
+def test_bench_plain_run_times_the_steps_and_dumps_the_last_frame(tmp_path):
+    """plain `python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR`: the line holds the headline figure and none of what
+    --full adds, `value` is the frame's rays over `ms_per_step`, and DIR holds the last timed frame as float32 .npy files — the
+    frame the engine renders in this process from the same weights and rays."""
+    import json
+    import subprocess
+    import sys
+
+    import numpy as np
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs",
+           str(tmp_path / "out")]
+    r = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    line = json.loads([ln for ln in r.stdout.splitlines() if ln.strip()][-1])
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["n_gpus"] == 1 and line["dtype"] == "f32"
+    assert line["value"] == pytest.approx(640000 / (line["ms_per_step"] * 1e-3), rel=1e-3)
+    assert line["roofline"]["frac"] > 0
+    for k in ("cpu_baseline", "parity", "speedup_vs_cpu", "variants"):
+        assert k not in line, k
+
+    from thermo_nerf_amd import SceneBox, ThermalNerfModel, ThermalNerfModelConfig, synthetic
+    from thermo_nerf_amd.engine import RayRenderEngine
+
+    cfg = ThermalNerfModelConfig(num_nerf_samples_per_ray=192, eval_num_rays_per_chunk=640000, dense_grid_budget_mb=64,
+                                 field_dense_grid_budget_mb=16)
+    model = ThermalNerfModel(cfg, metadata={"thermal": []}, scene_box=SceneBox.unit(), num_train_data=8)
+    synthetic.fill_model_(model, "scene")
+    model = model.eval().to(DEV)
+    engine = RayRenderEngine(model, chunk=640000)
+    o, d, _ = synthetic.orbit_camera_rays(800, 800, view=0)
+    o, d = o.reshape(-1, 3).contiguous().to(DEV), d.reshape(-1, 3).contiguous().to(DEV)
+    want = engine.allocate_outputs(o.shape[0], DEV)
+    engine.render(o, d, out=want)
+    torch.cuda.synchronize()
+    assert sorted(p.name for p in (tmp_path / "out").iterdir()) == sorted(k + ".npy" for k in want)
+    for k, w in want.items():
+        got = np.load(tmp_path / "out" / (k + ".npy"))
+        assert got.dtype == np.float32 and got.shape == tuple(w.shape), k
+        assert np.isfinite(got).all(), k
+        np.testing.assert_allclose(got, w.cpu().numpy(), rtol=1e-5, atol=1e-6, err_msg=k)

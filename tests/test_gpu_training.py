@@ -1521,7 +1521,15 @@ def test_config3_step_size_fresh_batches_against_the_atomic_single_stream_taped_
                 differ = (g1[n] == 0) != (g == 0)
                 assert int(differ.sum()) <= max(64, int((g != 0).sum()) // 1000), (n, int(differ.sum()))
                 if differ.any():
-                    assert float(torch.maximum(g1[n].abs(), g.abs())[differ].max()) <= 1e-9 * float(g.abs().max()), n
+                    # such a rest is a rounding residue of its own level's sums, so it is held to one fp32 epsilon of that level's
+                    # largest entry (the coarse levels carry the table's largest gradients, up to 2.5e-4 after 50 steps; measured
+                    # at step 0: denormals and at most 1.2e-16 in a level whose largest entry is 1.1e-7)
+                    T = model.field.mlp_base.encoder.hash_table_size
+                    both = torch.maximum(g1[n].abs(), g.abs())
+                    level_max = both.view(-1, T, both.shape[-1]).amax(dim=(1, 2))
+                    level = differ.nonzero()[:, 0] // T
+                    over = both[differ] > torch.finfo(torch.float32).eps * level_max[level]
+                    assert not bool(over.any()), (n, both[differ][over].tolist(), level[over].tolist(), level_max.tolist())
         print(f"step {step}: worst relative gradient difference " + ", ".join(f"{n.split('.')[-3:]}: {v:.1e}" for n, v in
               sorted(worst.items(), key=lambda kv: -kv[1])[:4]))
         for n, v in worst.items():
