@@ -75,6 +75,20 @@ constexpr int BLOB_FLOATS = OFF_WTH + 64 + 4;     // 18024 floats = 72 096 B
 constexpr int OFF_SCRATCH = BLOB_FLOATS;          // per-wave [64] colour-layer bias of the current ray
 constexpr int LDS_FLOATS = OFF_SCRATCH + kWaves * 64;
 static_assert(BLOB_FLOATS % 4 == 0, "blob must be float4-copyable");
+// main_mfma_rays_kernel: one 512-thread block per CU (8 waves, 2 per SIMD) shares ONE copy of the blob's eval part — everything
+// before OFF_W_SH, then the two output layers moved down over W_SH / W_APP, which it does not read — and each wave keeps 3 of the 4
+// 32x32 tiles of its ray tile's colour-layer bias in LDS (48 values per lane, lane-private): in registers they would not fit beside
+// the hash phase's two level groups in flight at 2 waves/SIMD.
+constexpr int kRaysBlock = 512;
+constexpr int kRaysWaves = kRaysBlock / TN_WAVE;
+constexpr int RAYS_OFF_W3 = OFF_W_SH;
+constexpr int RAYS_OFF_WTH = RAYS_OFF_W3 + (OFF_WTH - OFF_W3);
+constexpr int RAYS_BLOB_FLOATS = RAYS_OFF_W3 + (BLOB_FLOATS - OFF_W3);  // 15 016 floats
+constexpr int RAYS_C0_SLOTS = 12;                                       // float4 slots per lane: c0 tiles (0,1), (1,0), (1,1)
+constexpr int RAYS_OFF_C0 = RAYS_BLOB_FLOATS;                           // [wave][slot][lane] float4
+constexpr int RAYS_LDS_FLOATS = RAYS_OFF_C0 + kRaysWaves * RAYS_C0_SLOTS * 64 * 4;
+static_assert(OFF_W_SH % 4 == 0 && OFF_W3 % 4 == 0 && RAYS_OFF_C0 % 4 == 0, "float4 staging");
+static_assert(RAYS_LDS_FLOATS * sizeof(float) <= 160 * 1024, "main_mfma_rays_kernel: LDS of one CU");
 
 __device__ __forceinline__ int crow(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
 // geo row (0 = raw density, 1..15 = geo features) fed by k-step j of the geo -> hidden layers in lane half h (see swap16 above)
@@ -499,8 +513,11 @@ __global__ void __launch_bounds__(kBlock, 2) main_mfma_kernel(MfmaArgs a) {
 // hash-grid cells, so a gather instruction touches a handful of cache lines instead of 64 (the ray-per-wave
 // form spreads its 64 lanes along one ray: every fine-level gather is 64 distinct lines and the kernel was bound
 // by the random-access rate of TCP/L2).  Compositing becomes a per-lane running sum — no cross-lane scan at all.
-// The per-ray SH(dir) contribution of the colour layer rides along as 8 extra k-steps (B operands built once per
-// ray group), so a pass is 416 32x32x2 + 64 16x16x4 MFMAs; the appearance term is folded into the bias by tn_field_prepare (eval).
+// The per-ray SH(dir) contribution of the colour layer is folded into a per-ray bias once per tile (8 SH k-steps = 32
+// 32x32x2 MFMAs on the layer's bias, kept in the layer's C/D layout), and every sample's colour layer starts from it as its C
+// operand, so a pass is 384 32x32x2 + 64 16x16x4 MFMAs (was 416 + 64 with the SH k-steps in every sample); the appearance term
+// is folded into the bias by tn_field_prepare (eval).  The bias is 64 values per lane: 16 stay in registers, 48 in LDS (see
+// kRaysBlock), so the hash phase keeps its two groups of LG levels in flight at 2 waves/SIMD.
 // ------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ float fast_sigmoid(float x) {
     // v_exp_f32 / v_rcp_f32 (1 ulp each): |error| < 3e-7 absolute on a value in (0,1)
@@ -538,13 +555,25 @@ __device__ __forceinline__ float2 out_dot_fast(const float *wrow, int h, const f
 // association of the same products (not bit-equal to the unsplit march: same tolerance, and the split count is a property of the
 // CALL, tn_render_sample_split, so parts of a call agree with the whole bit for bit).  The median needs the crossing of 0.5 by
 // the GLOBAL cumulative weight: every sample stores its segment-local one, the combine pass searches the segment that crosses.
+// one 32x32 C/D tile of the colour-layer bias from a lane's four LDS slots (p[0], p[64], p[128], p[192])
+__device__ __forceinline__ f32x16 c0_frag(const float4 *p) {
+    f32x16 v;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const float4 t = p[q * 64];
+        v[4 * q] = t.x; v[4 * q + 1] = t.y; v[4 * q + 2] = t.z; v[4 * q + 3] = t.w;
+    }
+    return v;
+}
+
 template <bool DENSE, bool SPLIT = false>
-__global__ void __launch_bounds__(kBlock, 2) main_mfma_rays_kernel(MfmaArgs a) {
+__global__ void __launch_bounds__(kRaysBlock, 1) main_mfma_rays_kernel(MfmaArgs a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     {
         const float4 *src = reinterpret_cast<const float4 *>(a.blob);
         float4 *dst = reinterpret_cast<float4 *>(lds);
-        for (int i = threadIdx.x; i < BLOB_FLOATS / 4; i += kBlock) dst[i] = src[i];
+        for (int i = threadIdx.x; i < RAYS_BLOB_FLOATS / 4; i += kRaysBlock)
+            dst[i] = src[i < OFF_W_SH / 4 ? i : i + (OFF_W3 - OFF_W_SH) / 4];
     }
     __syncthreads();
     const float *A = lds + OFF_A;
@@ -552,13 +581,14 @@ __global__ void __launch_bounds__(kBlock, 2) main_mfma_rays_kernel(MfmaArgs a) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, h = lane >> 5;
     const bool lin = a.lin != 0;
     const int S = a.S;
+    float4 *c0s = reinterpret_cast<float4 *>(lds + RAYS_OFF_C0) + wave * RAYS_C0_SLOTS * 64 + lane;  // slot q at c0s[q * 64]
     const long long groups = (a.R + 63) >> 6;
-    const long long stride = (long long)gridDim.x * kWaves;
+    const long long stride = (long long)gridDim.x * kRaysWaves;
     const int K = SPLIT ? a.split : 1;
     const long long vgroups = groups * K;
     float smin = INFINITY, smax = -INFINITY;
     long long mm_slot = 0;
-    for (long long vg = (long long)blockIdx.x * kWaves + wave; vg < vgroups; vg += stride) {
+    for (long long vg = (long long)blockIdx.x * kRaysWaves + wave; vg < vgroups; vg += stride) {
         const long long grp = SPLIT ? vg / K : vg;
         const int s0 = SPLIT ? (int)(vg - grp * K) * a.seg_len : 0;
         const int s1 = SPLIT ? (s0 + a.seg_len < S ? s0 + a.seg_len : S) : S;
@@ -574,9 +604,12 @@ __global__ void __launch_bounds__(kBlock, 2) main_mfma_rays_kernel(MfmaArgs a) {
         const float dx = a.dirs[rc * 3], dy = a.dirs[rc * 3 + 1], dz = a.dirs[rc * 3 + 2];
         const float s_near = spacing_fn(a.nears[rc], lin), s_far = spacing_fn(a.fars[rc], lin);
         const float *tb = a.spacing + tn_ws_bin(grp * 64, 0, S) + (rc - grp * 64);  // edge j at tb[j*64]
-        // SH(dir) of this lane's ray -> B operands of the 8 SH k-steps (constant over the sample loop)
-        float bs0[8], bs1[8];
+        // per-ray colour-layer bias c0[mt][nt] = b + W_sh . SH(dir) in the colour layer's C/D layout (column = ray 32 nt + (l & 31)):
+        // the 8 SH k-steps run once per tile; c0[0][0] stays in registers as the C operand of every sample's first colour MFMA, the
+        // other three tiles go to this lane's LDS slots and are read back into the layer's accumulators at every sample
+        f32x16 c00;
         {
+            f32x16 c0[2][2];
             float sx = dx, sy = dy, sz = dz;
             if (a.sh_shifted) {
                 sx = add_rn(sx, 1.0f) / 2.0f; sy = add_rn(sy, 1.0f) / 2.0f; sz = add_rn(sz, 1.0f) / 2.0f;
@@ -584,7 +617,28 @@ __global__ void __launch_bounds__(kBlock, 2) main_mfma_rays_kernel(MfmaArgs a) {
             float c[16];
             sh16(sx, sy, sz, c);
 #pragma unroll
-            for (int s = 0; s < 8; ++s) swap32(c[2 * s], c[2 * s + 1], bs0[s], bs1[s]);
+            for (int mt = 0; mt < 2; ++mt) {
+                c0[mt][0] = bias_frag(lds + OFF_B_C1_EVAL, mt, h);
+                c0[mt][1] = c0[mt][0];
+            }
+#pragma unroll
+            for (int s = 0; s < 8; ++s) {
+                float bs0, bs1;
+                swap32(c[2 * s], c[2 * s + 1], bs0, bs1);
+#pragma unroll
+                for (int mt = 0; mt < 2; ++mt) {
+                    const float aw = A[(A_SH + mt * 8 + s) * 64 + lane];
+                    MFMA32(c0[mt][0], aw, bs0);
+                    MFMA32(c0[mt][1], aw, bs1);
+                }
+            }
+            c00 = c0[0][0];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                c0s[(0 + q) * 64] = make_float4(c0[0][1][4 * q], c0[0][1][4 * q + 1], c0[0][1][4 * q + 2], c0[0][1][4 * q + 3]);
+                c0s[(4 + q) * 64] = make_float4(c0[1][0][4 * q], c0[1][0][4 * q + 1], c0[1][0][4 * q + 2], c0[1][0][4 * q + 3]);
+                c0s[(8 + q) * 64] = make_float4(c0[1][1][4 * q], c0[1][1][4 * q + 1], c0[1][1][4 * q + 2], c0[1][1][4 * q + 3]);
+            }
         }
         float en = spacing_to_eucl<true>(tb[(size_t)s0 * 64], s_near, s_far, lin);
         float accum = 0.0f, cum_w = 0.0f;  // sum of delta*sigma before this sample; running sum of weights
@@ -630,20 +684,19 @@ __global__ void __launch_bounds__(kBlock, 2) main_mfma_rays_kernel(MfmaArgs a) {
             float raw, unused;
             swap32(g[0][0], g[1][0], raw, unused);
             const float dens = mul_rn(mul_rn(a.avg, __expf(raw)), sel);
-            {   // colour: [geo | SH] -> 64 -> 64 -> 3
-                f32x16 x1[2][2], x2[2][2];
-                layer_geo(A, A_C1, lds + OFF_B_C1_EVAL, lane, h, g, x1);
+            {   // colour: geo (on the per-ray bias c0) -> 64 -> 64 -> 3
+                f32x16 x1[2][2] = {{c00, c0_frag(c0s)}, {c0_frag(c0s + 4 * 64), c0_frag(c0s + 8 * 64)}}, x2[2][2];
 #pragma unroll
                 for (int s = 0; s < 8; ++s) {
 #pragma unroll
                     for (int mt = 0; mt < 2; ++mt) {
-                        const float aw = A[(A_SH + mt * 8 + s) * 64 + lane];
-                        MFMA32(x1[mt][0], aw, bs0[s]);
-                        MFMA32(x1[mt][1], aw, bs1[s]);
+                        const float aw = A[(A_C1 + mt * 8 + s) * 64 + lane];
+                        MFMA32(x1[mt][0], aw, g[0][s]);
+                        MFMA32(x1[mt][1], aw, g[1][s]);
                     }
                 }
                 layer64(A, A_C2, lds + OFF_B_C2, lane, h, x1, x2);
-                const float *w3 = lds + OFF_W3;
+                const float *w3 = lds + RAYS_OFF_W3;
                 cr = fast_sigmoid(combine_halves(out_dot_fast<0>(w3, h, x2)) + w3[192]);
                 cg = fast_sigmoid(combine_halves(out_dot_fast<0>(w3 + 64, h, x2)) + w3[193]);
                 cb = fast_sigmoid(combine_halves(out_dot_fast<0>(w3 + 128, h, x2)) + w3[194]);
@@ -652,7 +705,7 @@ __global__ void __launch_bounds__(kBlock, 2) main_mfma_rays_kernel(MfmaArgs a) {
                 f32x16 x1[2][2], x2[2][2];
                 layer_geo(A, A_T1, lds + OFF_B_T1, lane, h, g, x1);
                 layer64(A, A_T2, lds + OFF_B_T2, lane, h, x1, x2);
-                const float *wt = lds + OFF_WTH;
+                const float *wt = lds + RAYS_OFF_WTH;
                 th = combine_halves(out_dot_fast<1>(wt, h, x2)) + wt[64];
             }
 #if TN_MFMA_MLP_PRIO
@@ -1066,6 +1119,8 @@ int launch_main_mfma(const tn_thermal_field *field, const tn_render_config *cfg,
     a.split = 1; a.seg_len = a.S; a.seg_rec = nullptr; a.seg_cum = nullptr;
     const size_t smem = (size_t)LDS_FLOATS * sizeof(float);
     const long long cap = 256LL * 2;  // 2 resident blocks per CU (LDS 77 KB each)
+    const size_t smem_rays = (size_t)RAYS_LDS_FLOATS * sizeof(float);
+    const long long cap_rays = 256;  // main_mfma_rays_kernel: 1 resident block of 8 waves per CU (LDS 155 KB)
     // 1.5 ms floor of the tile march vs 0.16 ms at 4096 rays
     const bool small_call = tn_render_kernel_form(field, cfg, num_rays, 1) == 2;
     if (!cfg->training && !out->weights[2] && !small_call) {
@@ -1077,28 +1132,29 @@ int launch_main_mfma(const tn_thermal_field *field, const tn_render_config *cfg,
             a.split = (a.S + a.seg_len - 1) / a.seg_len;  // (no empty segment)
             a.seg_rec = seg_scratch;
             a.seg_cum = seg_scratch + (size_t)groups * a.split * SEG_ROWS * 64;
-            if (!(dense ? tn_ensure_dynamic_lds<main_mfma_rays_kernel<true, true>>(smem) : tn_ensure_dynamic_lds<main_mfma_rays_kernel<false, true>>(smem)))
+            if (!(dense ? tn_ensure_dynamic_lds<main_mfma_rays_kernel<true, true>>(smem_rays)
+                        : tn_ensure_dynamic_lds<main_mfma_rays_kernel<false, true>>(smem_rays)))
                 return TN_ERR_LAUNCH;
-            const long long need = (groups * a.split + kWaves - 1) / kWaves;
-            const unsigned grid = (unsigned)(need < cap ? (need < 1 ? 1 : need) : cap);
+            const long long need = (groups * a.split + kRaysWaves - 1) / kRaysWaves;
+            const unsigned grid = (unsigned)(need < cap_rays ? (need < 1 ? 1 : need) : cap_rays);
             if (dense)
-                hipLaunchKernelGGL((main_mfma_rays_kernel<true, true>), dim3(grid), dim3(kBlock), smem, stream, a);
+                hipLaunchKernelGGL((main_mfma_rays_kernel<true, true>), dim3(grid), dim3(kRaysBlock), smem_rays, stream, a);
             else
-                hipLaunchKernelGGL((main_mfma_rays_kernel<false, true>), dim3(grid), dim3(kBlock), smem, stream, a);
+                hipLaunchKernelGGL((main_mfma_rays_kernel<false, true>), dim3(grid), dim3(kRaysBlock), smem_rays, stream, a);
             hipLaunchKernelGGL(segments_combine_kernel, dim3((unsigned)((num_rays + 255) / 256)), dim3(256), 0, stream, a);
             if (hipGetLastError() != hipSuccess) return TN_ERR_LAUNCH;
             return TN_OK;
         }
         a.split = 1;
-        if (!(dense ? tn_ensure_dynamic_lds<main_mfma_rays_kernel<true>>(smem) : tn_ensure_dynamic_lds<main_mfma_rays_kernel<false>>(smem)))
+        if (!(dense ? tn_ensure_dynamic_lds<main_mfma_rays_kernel<true>>(smem_rays) : tn_ensure_dynamic_lds<main_mfma_rays_kernel<false>>(smem_rays)))
             return TN_ERR_LAUNCH;
         const long long groups = (num_rays + 63) / 64;
-        const long long need = (groups + kWaves - 1) / kWaves;
-        const unsigned grid = (unsigned)(need < cap ? (need < 1 ? 1 : need) : cap);
+        const long long need = (groups + kRaysWaves - 1) / kRaysWaves;
+        const unsigned grid = (unsigned)(need < cap_rays ? (need < 1 ? 1 : need) : cap_rays);
         if (dense)
-            hipLaunchKernelGGL(main_mfma_rays_kernel<true>, dim3(grid), dim3(kBlock), smem, stream, a);
+            hipLaunchKernelGGL(main_mfma_rays_kernel<true>, dim3(grid), dim3(kRaysBlock), smem_rays, stream, a);
         else
-            hipLaunchKernelGGL(main_mfma_rays_kernel<false>, dim3(grid), dim3(kBlock), smem, stream, a);
+            hipLaunchKernelGGL(main_mfma_rays_kernel<false>, dim3(grid), dim3(kRaysBlock), smem_rays, stream, a);
         if (hipGetLastError() != hipSuccess) return TN_ERR_LAUNCH;
         return TN_OK;
     }
