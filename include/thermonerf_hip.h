@@ -215,6 +215,23 @@ size_t tn_ssim_workspace_bytes(int32_t height, int32_t width, int32_t channels);
 int tn_ssim_fwd(const float *pred, const float *target, int32_t height, int32_t width, int32_t channels, float data_range,
                 void *workspace, size_t workspace_bytes, float *out, void *stream);
 
+/* Frame finishing of the inference harness [REF thermo_nerf/render/renderer.py:189-199]: src [n, channels] device floats
+ * (channels 1 or 3) -> dst [n, 3] uint8, on the device, every step one correctly rounded fp32 operation:
+ *   TN_FRAME_SCALE  `(x * 255).astype(np.uint8)`, one channel replicated to three [REF :191-192,198]; outside [0, 256), where
+ *                   numpy's cast is undefined: saturated to [0, 255], NaN -> 0.
+ *   TN_FRAME_LUT    `(cmap(x[:, :, 0])[:, :, :3] * 255).astype(np.uint8)` for a 256-entry matplotlib ListedColormap [REF :193-196]:
+ *                   i = trunc(x * 256) (256 -> 255), dst = table[i]; x < 0 -> entry 0, i > 255 -> entry 255, NaN -> (0, 0, 0);
+ *                   `table` = uint8 [256, 3] = trunc(colours * 255).  Channel 0 is looked up.
+ *   TN_FRAME_DEPTH  NS colormaps.apply_depth_colormap: t = clip((d - near) / ((far - near) + 1e-10), 0, 1), NaN -> 0;
+ *                   c = table[trunc(t * 255)] (`table` = float [256, 3]); TN_FRAME_SCALE of c * acc + (1 - acc).
+ *                   near_far = 2 device floats (near, far), acc [n] device floats; both NULL otherwise.
+ * dst may start at any byte (a piece of a frame): whole dwords are written wherever 4 pixels share three of them. */
+#define TN_FRAME_SCALE 0
+#define TN_FRAME_LUT 1
+#define TN_FRAME_DEPTH 2
+int tn_frame_to_rgb8(const float *src, int64_t num_pixels, int32_t channels, int32_t mode, const void *table, const float *acc,
+                     const float *near_far, uint8_t *dst, void *stream);
+
 /* ------------------------------------------------------------------------------------------------------
  * Fused forward: Model.forward (collider) + ThermalNerfModel.get_outputs
  * [REF thermal_nerf_model.py:210-275]
