@@ -35,11 +35,32 @@
 // frame (coherent rays, the kernel waits for the matrix pipe): 1 beside MLP priority 1 costs 3 % (31.4 against 30.6 ms), beside
 // MLP priority 2 nothing: off.  Training forward (incoherent rays, the kernel waits for its gathers): the step 2.49-2.51 ->
 // 2.43-2.46 ms at S=192 (tools/ab_train.sh, two interleaved repetitions): on.
+// main_mfma_rays_kernel raises the priority once more for the thermal branch, the last third of the block.  The two waves of a SIMD
+// settle half a sample apart on their own (tools/field_stamps.py: the offset is 0.5 of a period from the second sample of a tile on
+// and stays there), so a wave's hash phase runs under its partner's MLP block; but the hash phase is the shorter of the two, and
+// the partner that comes out of it starts its base layers beside the first wave's thermal branch.  At equal priority the two MFMA
+// streams and the thermal sigmoids take turns by age; with the wave that is nearly done in front, it leaves the block sooner and its
+// partner's matrix work follows in one piece.  Field kernel per 640 k-ray launch at S=192: 28.87-28.97 -> 28.25-28.35 ms with
+// (MLP, thermal) = (1, 2); (1, 3) and (2, 3) the same, (3, 3) and a falling (3, 2, 1) nothing, raising the colour branch too
+// (1, 2, 3) 28.50-28.63 (profiles/field_idle_ab.txt; outputs bit-identical).
+#ifndef TN_MFMA_THERMAL_PRIO
+#define TN_MFMA_THERMAL_PRIO (TN_MFMA_MLP_PRIO ? TN_MFMA_MLP_PRIO + 1 : 0)
+#endif
 #ifndef TN_EVAL_GATHER_PRIO
 #define TN_EVAL_GATHER_PRIO 0
 #endif
 #ifndef TN_TRAIN_GATHER_PRIO
 #define TN_TRAIN_GATHER_PRIO 1
+#endif
+
+// main_mfma_rays_kernel's base2_tiles: ReLUs, lane swaps and MFMAs of half a hidden layer in three runs (0 = interleaved)
+#ifndef TN_BASE2_STAGED
+#define TN_BASE2_STAGED 1
+#endif
+// main_mfma_rays_kernel: the thermal hidden layer's weights and bias carry the sigmoid's factor -log2(e) in the kernel's LDS copy
+// (0 = the blob's values, one v_mul more per sigmoid)
+#ifndef TN_T2_PRESCALE
+#define TN_T2_PRESCALE 1
 #endif
 
 using namespace tn;
@@ -225,13 +246,46 @@ __device__ __forceinline__ void swap16(float a, float b, float &even, float &odd
 // mlp_base layer 1 (64 -> 1 + geo = 16 rows, no activation) on relu(h1), then its outputs re-laid as the B operands of the
 // eight k-steps of the geo -> hidden layers: gb[nt][j] (k rows grow(j, 0) | grow(j, 1)).  gb[nt][0] lanes 0-31 = raw density.
 // G[T][q]: row 4 (l >> 4) + q of mlp_base's 16 outputs for sample 16 T + (l & 15)
+// STAGED (main_mfma_rays_kernel): see below; every other caller keeps the interleaved order it was tuned with
+template <bool STAGED = false>
 __device__ __forceinline__ void base2_tiles(const float *A, const float *bias16, int lane, const f32x16 (&h1)[2][2],
                                             f32x4 (&G)[4]) {
     const float4 bq = *reinterpret_cast<const float4 *>(bias16 + 4 * (lane >> 4));  // C rows 4 (l >> 4) + q
     const f32x4 b4 = {bq.x, bq.y, bq.z, bq.w};
     G[0] = b4; G[1] = b4; G[2] = b4; G[3] = b4;  // 16-sample tiles 0..3
+    // STAGED, per half of the hidden layer: all ReLUs, then all swaps, then the MFMAs (each accumulator's k order is unchanged).
+    // Interleaved as in the second loop, every v_permlane16_swap waits two states for the v_max that feeds it and every MFMA one for
+    // its swap: 50 s_nop fewer per sample in main_mfma_rays_kernel, 28.33-28.35 -> 28.29-28.30 ms per launch
 #pragma unroll
-    for (int mi = 0; mi < 2; ++mi) {
+    for (int mi = 0; STAGED && mi < 2; ++mi) {
+        float t[8][2][2], lo[8][2], hi[8][2];
+#pragma unroll
+        for (int rp = 0; rp < 8; ++rp) {
+#pragma unroll
+            for (int nt = 0; nt < 2; ++nt) {
+                t[rp][nt][0] = relu_bits(h1[mi][nt][2 * rp]);
+                t[rp][nt][1] = relu_bits(h1[mi][nt][2 * rp + 1]);
+            }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int rp = 0; rp < 8; ++rp) {
+#pragma unroll
+            for (int nt = 0; nt < 2; ++nt) swap16(t[rp][nt][0], t[rp][nt][1], lo[rp][nt], hi[rp][nt]);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int rp = 0; rp < 8; ++rp) {
+            const float aw = A[(A_BASE2 + mi * 8 + rp) * 64 + lane];
+#pragma unroll
+            for (int nt = 0; nt < 2; ++nt) {
+                MFMA16(G[2 * nt], aw, lo[rp][nt]);
+                MFMA16(G[2 * nt + 1], aw, hi[rp][nt]);
+            }
+        }
+    }
+#pragma unroll
+    for (int mi = 0; !STAGED && mi < 2; ++mi) {
 #pragma unroll
         for (int rp = 0; rp < 8; ++rp) {
             const float aw = A[(A_BASE2 + mi * 8 + rp) * 64 + lane];
@@ -252,10 +306,11 @@ __device__ __forceinline__ void geo_relayout(const f32x4 (&G)[4], float (&gb)[2]
         for (int q = 0; q < 4; ++q) swap16(G[2 * nt][q], G[2 * nt + 1][q], gb[nt][2 * q], gb[nt][2 * q + 1]);
     }
 }
+template <bool STAGED = false>
 __device__ __forceinline__ void base2_geo(const float *A, const float *bias16, int lane, const f32x16 (&h1)[2][2],
                                           float (&gb)[2][8]) {
     f32x4 G[4];
-    base2_tiles(A, bias16, lane, h1, G);
+    base2_tiles<STAGED>(A, bias16, lane, h1, G);
     geo_relayout(G, gb);
 }
 
@@ -524,7 +579,13 @@ __device__ __forceinline__ float fast_sigmoid(float x) {
     return __builtin_amdgcn_rcpf(1.0f + __expf(-x));
 }
 
-template <int ACT>  // 0 relu, 1 fast sigmoid
+// the same on an argument that already carries the factor -log2(e): the thermal hidden layer's weights and bias are scaled by it
+// when main_mfma_rays_kernel stages its LDS copy of the blob, so the accumulator goes to v_exp_f32 as it is
+__device__ __forceinline__ float fast_sigmoid_prescaled(float x) {
+    return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(x));
+}
+
+template <int ACT>  // 0 relu, 1 fast sigmoid, 2 fast sigmoid of a pre-scaled argument
 __device__ __forceinline__ float2 out_dot_fast(const float *wrow, int h, const f32x16 (&x)[2][2]) {
     float p0 = 0.0f, p1 = 0.0f;
 #pragma unroll
@@ -536,8 +597,8 @@ __device__ __forceinline__ float2 out_dot_fast(const float *wrow, int h, const f
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 const float a0 = x[mt][0][4 * q + e], a1 = x[mt][1][4 * q + e];
-                const float v0 = ACT ? fast_sigmoid(a0) : relu_bits(a0);
-                const float v1 = ACT ? fast_sigmoid(a1) : relu_bits(a1);
+                const float v0 = ACT == 2 ? fast_sigmoid_prescaled(a0) : ACT ? fast_sigmoid(a0) : relu_bits(a0);
+                const float v1 = ACT == 2 ? fast_sigmoid_prescaled(a1) : ACT ? fast_sigmoid(a1) : relu_bits(a1);
                 p0 = fmaf(ww[e], v0, p0);
                 p1 = fmaf(ww[e], v1, p1);
             }
@@ -566,14 +627,43 @@ __device__ __forceinline__ f32x16 c0_frag(const float4 *p) {
     return v;
 }
 
+// TN_FIELD_STAMPS=1 (make EXTRA=-DTN_FIELD_STAMPS=1; tools/field_stamps.py; never the shipped object): waves 0 and 4 of the first
+// kStampBlocks workgroups (one SIMD pair each) take s_memtime at the phase boundaries of every sample of their second tile and leave
+// the low 32 bits in tn_field_stamp_buf [block][partner][sample][slot].  Slots: 0 top of the sample | per level group gi: 1 + 2 gi
+// taps computed and gathers issued, 2 + 2 gi first level of the group blended (= the gather wait) | 9 hash phase done | 10 base
+// layers | 11 colour head | 12 colour output layer | 13 thermal head | 14 thermal sigmoids + output | 15 compositing done.
+#ifndef TN_FIELD_STAMPS
+#define TN_FIELD_STAMPS 0
+#endif
+#if TN_FIELD_STAMPS
+constexpr int kStampBlocks = 16, kStampSamples = 192, kStampSlots = 16;
+__device__ unsigned int tn_field_stamp_buf[kStampBlocks * 2 * kStampSamples * kStampSlots];
+#define TN_STAMP(k)                                            \
+    do {                                                       \
+        __builtin_amdgcn_sched_barrier(0);                     \
+        stamp[k] = (unsigned int)__builtin_amdgcn_s_memtime(); \
+        __builtin_amdgcn_sched_barrier(0);                     \
+    } while (0)
+#else
+#define TN_STAMP(k) do { } while (0)
+#endif
+
 template <bool DENSE, bool SPLIT = false>
 __global__ void __launch_bounds__(kRaysBlock, 1) main_mfma_rays_kernel(MfmaArgs a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     {
         const float4 *src = reinterpret_cast<const float4 *>(a.blob);
         float4 *dst = reinterpret_cast<float4 *>(lds);
-        for (int i = threadIdx.x; i < RAYS_BLOB_FLOATS / 4; i += kRaysBlock)
-            dst[i] = src[i < OFF_W_SH / 4 ? i : i + (OFF_W3 - OFF_W_SH) / 4];
+        for (int i = threadIdx.x; i < RAYS_BLOB_FLOATS / 4; i += kRaysBlock) {
+            float4 v = src[i < OFF_W_SH / 4 ? i : i + (OFF_W3 - OFF_W_SH) / 4];
+#if TN_T2_PRESCALE
+            if ((i >= A_T2 * 16 && i < A_SH * 16) || (i >= OFF_B_T2 / 4 && i < OFF_B_T2 / 4 + 16)) {
+                const float k = -1.44269504088896341f;  // -log2(e)
+                v = make_float4(mul_rn(v.x, k), mul_rn(v.y, k), mul_rn(v.z, k), mul_rn(v.w, k));
+            }
+#endif
+            dst[i] = v;
+        }
     }
     __syncthreads();
     const float *A = lds + OFF_A;
@@ -588,7 +678,14 @@ __global__ void __launch_bounds__(kRaysBlock, 1) main_mfma_rays_kernel(MfmaArgs 
     const long long vgroups = groups * K;
     float smin = INFINITY, smax = -INFINITY;
     long long mm_slot = 0;
+#if TN_FIELD_STAMPS
+    unsigned int stamp[kStampSlots] = {};
+    int tile_no = -1;
+#endif
     for (long long vg = (long long)blockIdx.x * kRaysWaves + wave; vg < vgroups; vg += stride) {
+#if TN_FIELD_STAMPS
+        ++tile_no;
+#endif
         const long long grp = SPLIT ? vg / K : vg;
         const int s0 = SPLIT ? (int)(vg - grp * K) * a.seg_len : 0;
         const int s1 = SPLIT ? (s0 + a.seg_len < S ? s0 + a.seg_len : S) : S;
@@ -649,6 +746,7 @@ __global__ void __launch_bounds__(kRaysBlock, 1) main_mfma_rays_kernel(MfmaArgs 
         // round trip is not the first thing a sample waits for (field kernel 32.0 -> 31.75 ms per 640 k rays at S=192)
         float sb_next = tb[(size_t)(s0 + 1) * 64];
         for (int i = s0; i < s1; ++i) {
+            TN_STAMP(0);
             const float st = en;
             en = spacing_to_eucl<true>(sb_next, s_near, s_far, lin);
             sb_next = tb[(size_t)(i + 2 <= S ? i + 2 : S) * 64];
@@ -659,8 +757,19 @@ __global__ void __launch_bounds__(kRaysBlock, 1) main_mfma_rays_kernel(MfmaArgs 
             float bt0[16], bt1[16];
             // index arithmetic | gathers | interpolation in explicit stages, two groups of LG levels in flight; DENSE: the first
             // kFieldDense levels come from the dense re-layout (4 aligned 16-byte gathers per level instead of 8 8-byte ones)
+#if TN_FIELD_STAMPS
+            hash_encode_pipelined_raw<L16, LG, DENSE ? kFieldDense : 0, TN_EVAL_GATHER_PRIO>(
+                a.g, px, py, pz, [&](int l, const HashTaps &t, const float2 (&fc)[8]) {
+                    if (l % LG == 0) TN_STAMP(1 + 2 * (l / LG));
+                    const float2 f = hash_blend(t, fc);
+                    if (l % LG == 0) TN_STAMP(2 + 2 * (l / LG));
+                    swap32(f.x, f.y, bt0[l], bt1[l]);
+                });
+            TN_STAMP(9);
+#else
             hash_encode_pipelined<L16, LG, DENSE ? kFieldDense : 0, TN_EVAL_GATHER_PRIO>(a.g, px, py, pz,
                                                                     [&](int l, float2 f) { swap32(f.x, f.y, bt0[l], bt1[l]); });
+#endif
 #if TN_MFMA_MLP_PRIO
             __builtin_amdgcn_s_setprio(TN_MFMA_MLP_PRIO);
 #endif
@@ -680,10 +789,11 @@ __global__ void __launch_bounds__(kRaysBlock, 1) main_mfma_rays_kernel(MfmaArgs 
                 }
             }
             float g[2][8];
-            base2_geo(A, lds + OFF_B_BASE2, lane, h1, g);
+            base2_geo<TN_BASE2_STAGED != 0>(A, lds + OFF_B_BASE2, lane, h1, g);
             float raw, unused;
             swap32(g[0][0], g[1][0], raw, unused);
             const float dens = mul_rn(mul_rn(a.avg, __expf(raw)), sel);
+            TN_STAMP(10);
             {   // colour: geo (on the per-ray bias c0) -> 64 -> 64 -> 3
                 f32x16 x1[2][2] = {{c00, c0_frag(c0s)}, {c0_frag(c0s + 4 * 64), c0_frag(c0s + 8 * 64)}}, x2[2][2];
 #pragma unroll
@@ -696,17 +806,24 @@ __global__ void __launch_bounds__(kRaysBlock, 1) main_mfma_rays_kernel(MfmaArgs 
                     }
                 }
                 layer64(A, A_C2, lds + OFF_B_C2, lane, h, x1, x2);
+                TN_STAMP(11);
                 const float *w3 = lds + RAYS_OFF_W3;
                 cr = fast_sigmoid(combine_halves(out_dot_fast<0>(w3, h, x2)) + w3[192]);
                 cg = fast_sigmoid(combine_halves(out_dot_fast<0>(w3 + 64, h, x2)) + w3[193]);
                 cb = fast_sigmoid(combine_halves(out_dot_fast<0>(w3 + 128, h, x2)) + w3[194]);
+                TN_STAMP(12);
             }
+#if TN_MFMA_THERMAL_PRIO != TN_MFMA_MLP_PRIO
+            __builtin_amdgcn_s_setprio(TN_MFMA_THERMAL_PRIO);
+#endif
             {   // thermal: geo -> 64 -> 64 sigmoid -> 1
                 f32x16 x1[2][2], x2[2][2];
                 layer_geo(A, A_T1, lds + OFF_B_T1, lane, h, g, x1);
                 layer64(A, A_T2, lds + OFF_B_T2, lane, h, x1, x2);
+                TN_STAMP(13);
                 const float *wt = lds + RAYS_OFF_WTH;
-                th = combine_halves(out_dot_fast<1>(wt, h, x2)) + wt[64];
+                th = combine_halves(out_dot_fast<TN_T2_PRESCALE ? 2 : 1>(wt, h, x2)) + wt[64];
+                TN_STAMP(14);
             }
 #if TN_MFMA_MLP_PRIO
             __builtin_amdgcn_s_setprio(0);
@@ -729,6 +846,15 @@ __global__ void __launch_bounds__(kRaysBlock, 1) main_mfma_rays_kernel(MfmaArgs 
             wsteps += mul_rn(wi, step);
             smin = fminf(smin, step);
             smax = fmaxf(smax, step);
+#if TN_FIELD_STAMPS
+            TN_STAMP(15);
+            if (blockIdx.x < kStampBlocks && (wave & 3) == 0 && tile_no == 1 && i < kStampSamples && lane < kStampSlots) {
+                unsigned int v = stamp[0];
+#pragma unroll
+                for (int k = 1; k < kStampSlots; ++k) v = lane == k ? stamp[k] : v;
+                tn_field_stamp_buf[((blockIdx.x * 2 + (wave >> 2)) * kStampSamples + i) * kStampSlots + lane] = v;
+            }
+#endif
             if (SPLIT) {  // (the launch guarantees no weights output and no early termination in this form)
                 a.seg_cum[((size_t)grp * S + i) * 64 + lane] = cum_w;
                 continue;
@@ -1169,6 +1295,13 @@ int launch_main_mfma(const tn_thermal_field *field, const tn_render_config *cfg,
 }  // namespace tn
 
 extern "C" {
+#if TN_FIELD_STAMPS
+// instrumented builds only: copies tn_field_stamp_buf [16 blocks][2 partners][192 samples][16 slots] to the host
+int tn_field_stamps_read(unsigned int *dst, size_t count) {
+    if (hipDeviceSynchronize() != hipSuccess) return TN_ERR_LAUNCH;
+    return hipMemcpyFromSymbol(dst, HIP_SYMBOL(tn_field_stamp_buf), count * sizeof(unsigned int)) == hipSuccess ? TN_OK : TN_ERR_LAUNCH;
+}
+#endif
 
 int tn_field_fwd_taped(const tn_thermal_field *f, const float *positions, const float *directions,
                        const int32_t *camera_indices, int64_t num_rays, int32_t n, float *enc, float *selector, float *h1,
