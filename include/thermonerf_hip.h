@@ -232,6 +232,35 @@ int tn_ssim_fwd(const float *pred, const float *target, int32_t height, int32_t 
 int tn_frame_to_rgb8(const float *src, int64_t num_pixels, int32_t channels, int32_t mode, const void *table, const float *acc,
                      const float *near_far, uint8_t *dst, void *stream);
 
+/* Foreground threshold of the evaluation harness [REF thermo_nerf/thermal_nerf/calculate_threshold.py:29-38]: for each of
+ * num_images grey images, the Otsu threshold cv2.threshold(image, 0, 255, THRESH_BINARY + THRESH_OTSU) returns — an integer
+ * in [0, 255]; the reference averages them over the dataset and divides by 255 (the host does that part).
+ *   pixels      device bytes of all images back to back; an image may start at any byte alignment.
+ *   offsets     HOST array of num_images + 1 increasing pixel offsets into `pixels` (image k = [offsets[k], offsets[k+1])),
+ *               read during the call and handed to the kernels by value, as the Adam step's descriptors are: the host can
+ *               refuse an unsupported extent and size the grid without a device read-back.
+ *   histograms  device uint32 [num_images, 256], caller-provided scratch AND output: cleared by the call itself, then the
+ *               exact count of every grey level (integer atomics: independent of the order of arrival).
+ *   thresholds  device int32 [num_images].
+ * Queued on `stream`; no host synchronisation inside the call.
+ * The threshold is the recurrence of OpenCV 4.x getThreshVal_Otsu_8u (imgproc/thresh.cpp) [recall], h = the histogram:
+ *     n = sum h[i];  scale = 1.0 / n;  mu = (sum over i = 0..255 ascending of i * h[i]) * scale
+ *     mu1 = 0, q1 = 0, max_sigma = 0, max_val = 0
+ *     for i = 0 .. 255:
+ *         p = h[i] * scale;  mu1 = mu1 * q1;  q1 = q1 + p;  q2 = 1 - q1
+ *         if min(q1, q2) < FLT_EPSILON or max(q1, q2) > 1 - FLT_EPSILON: continue      (mu1 stays multiplied)
+ *         mu1 = (mu1 + i * p) / q1;  mu2 = (mu - q1 * mu1) / q2
+ *         sigma = ((q1 * q2) * (mu1 - mu2)) * (mu1 - mu2)
+ *         if sigma > max_sigma: max_sigma = sigma; max_val = i
+ *     threshold = max_val
+ * in fp64, every step ONE correctly rounded operation in the order and association written.  Histograms with empty bins have
+ * plateaus of mathematically equal sigma on which the last bit decides which index the strict > keeps: the order of
+ * operations is part of the definition.  A constant image gives 0.
+ * TN_ERR_SHAPE: num_images < 1, a negative or decreasing offset, an image without pixels; TN_ERR_UNSUPPORTED: an image of
+ * 2^32 pixels or more (a bin is 32 bits wide). */
+int tn_otsu_thresholds(const uint8_t *pixels, const int64_t *offsets, int32_t num_images, uint32_t *histograms,
+                       int32_t *thresholds, void *stream);
+
 /* ------------------------------------------------------------------------------------------------------
  * Fused forward: Model.forward (collider) + ThermalNerfModel.get_outputs
  * [REF thermal_nerf_model.py:210-275]

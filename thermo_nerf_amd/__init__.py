@@ -7,6 +7,7 @@ nerfstudio samplers/renderers they call) and routes every arithmetic step to han
 fallback: without the shared object, or on a CPU tensor, calls raise.
 """
 from .rendered_image_modalities import RenderedImageModality  # noqa: F401
+from .model_type import ModelType  # noqa: F401
 from .rays import Frustums, RayBundle, RaySamples  # noqa: F401
 from .scene import NearFarCollider, SceneBox, SceneContraction  # noqa: F401
 from .fields import FieldHeadNames, HashMLPDensityField  # noqa: F401
