@@ -43,8 +43,11 @@ typedef struct tn_hashgrid {
     int32_t num_levels;            /* 1..16                                                        */
     int32_t log2_hashmap_size;     /* 1..24                                                        */
     /* optional re-laid ("dense") copy of the coarse levels produced by tn_hashgrid_prepare: for level
-     * l < num_dense_levels, dense + dense_offset[l] holds a [(res+2)^3, 2] x-major / z-fastest grid with
-     * dense[x][y][z] = table[hash(x,y,z)] — a pure layout change, results are bit-identical.        */
+     * l < num_dense_levels, dense + dense_offset[l] holds a [(res+2)^3] x-major / z-fastest grid of
+     * 16-byte elements derived from table[hash(x,y,z)].  What an element holds is a PRIVATE layout
+     * between tn_hashgrid_prepare and the kernels (today: the entry and the difference to its
+     * x-neighbour); callers only allocate the buffer and pass the struct on.  Results are
+     * bit-identical to the hashed tables'.                                                          */
     const float *dense;
     int64_t dense_offset[TN_MAX_LEVELS]; /* in float2 elements                                      */
     int32_t dense_res[TN_MAX_LEVELS];    /* grid side (= scalings[l] + 2)                           */

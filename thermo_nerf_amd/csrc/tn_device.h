@@ -155,37 +155,41 @@ __device__ __forceinline__ float2 encode_level(const Grid &g, int l, float px, f
     const float ox = __builtin_amdgcn_fractf(sx), oy = __builtin_amdgcn_fractf(sy), oz = __builtin_amdgcn_fractf(sz);
     float2 f0, f1, f2, f3, f4, f5, f6, f7;
     if (DENSE) {
-        // dense[x][y][z] = table[hash(x,y,z)]; ceil corner == floor+1 whenever its weight is non-zero
+        // ceil corner == floor+1 whenever its weight is non-zero.  A dense element (16 bytes, indexed [x][y][z], z fastest) is
+        // (e, d) = (table[hash(x,y,z)], table[hash(x+1,y,z)] - table[hash(x,y,z)]): tn_prepare.hip forms the x stage's a - b once
         const int res = g.dense_res[l];
         const float4 *d = reinterpret_cast<const float4 *>(g.dense) + g.dense_off[l];
-        // every dense element is the pair (entry(z), entry(z+1)): the (.,.,f) and (.,.,c) corners are ONE aligned 16-byte load
-        float4 v00, v01, v10, v11;
         if (FAST) {
+            // four aligned 16-byte loads from the x0 plane; the slot of each lerp pair's floor corner (f3 f2 f6 f7) holds e, the
+            // slot of its ceil corner (f0 f1 f5 f4) holds d: the x stage below is fmaf(ox, d, e).
             // 32-bit byte offsets from a wave-uniform level base (scalar-base global_load), 24-bit multiplies (side <= 1024)
             const unsigned ures = (unsigned)res;
             const unsigned i00 = __umul24(__umul24((unsigned)(int)fxf, ures) + (unsigned)(int)fyf, ures) + (unsigned)(int)fzf;
-            const unsigned b00 = i00 << 4, sy = ures << 4, sx = __umul24(ures, ures) << 4;
+            const unsigned b00 = i00 << 4, b01 = b00 + (ures << 4);
             const char *db = reinterpret_cast<const char *>(d);
-            v00 = *reinterpret_cast<const float4 *>(db + b00);
-            v01 = *reinterpret_cast<const float4 *>(db + (b00 + sy));
-            v10 = *reinterpret_cast<const float4 *>(db + (b00 + sx));
-            v11 = *reinterpret_cast<const float4 *>(db + (b00 + sx + sy));
+            const float4 v00 = *reinterpret_cast<const float4 *>(db + b00), v0c = *reinterpret_cast<const float4 *>(db + b00 + 16);
+            const float4 v10 = *reinterpret_cast<const float4 *>(db + b01), v1c = *reinterpret_cast<const float4 *>(db + b01 + 16);
+            f6 = make_float2(v00.x, v00.y); f5 = make_float2(v00.z, v00.w);  // (y0, z0)
+            f2 = make_float2(v0c.x, v0c.y); f1 = make_float2(v0c.z, v0c.w);  // (y0, z1)
+            f7 = make_float2(v10.x, v10.y); f4 = make_float2(v10.z, v10.w);  // (y1, z0)
+            f3 = make_float2(v1c.x, v1c.y); f0 = make_float2(v1c.z, v1c.w);  // (y1, z1)
         } else {
+            // torch order needs the raw ceil-corner entries: the base halves of the eight elements, 8-byte loads
+            const float2 *d2 = reinterpret_cast<const float2 *>(d);
             const int fx = (int)fxf, fy = (int)fyf, fz = (int)fzf;
             const int i00 = (fx * res + fy) * res + fz;
             const int i10 = i00 + res * res;  // x+1
             const int i01 = i00 + res;        // y+1
             const int i11 = i10 + res;
-            v00 = d[i00]; v01 = d[i01]; v10 = d[i10]; v11 = d[i11];
+            f6 = d2[2 * i00];        // (f,f,f)
+            f2 = d2[2 * (i00 + 1)];  // (f,f,c)
+            f7 = d2[2 * i01];        // (f,c,f)
+            f3 = d2[2 * (i01 + 1)];  // (f,c,c)
+            f5 = d2[2 * i10];        // (c,f,f)
+            f1 = d2[2 * (i10 + 1)];  // (c,f,c)
+            f4 = d2[2 * i11];        // (c,c,f)
+            f0 = d2[2 * (i11 + 1)];  // (c,c,c)
         }
-        f6 = make_float2(v00.x, v00.y);  // (f,f,f)
-        f2 = make_float2(v00.z, v00.w);  // (f,f,c)
-        f7 = make_float2(v01.x, v01.y);  // (f,c,f)
-        f3 = make_float2(v01.z, v01.w);  // (f,c,c)
-        f5 = make_float2(v10.x, v10.y);  // (c,f,f)
-        f1 = make_float2(v10.z, v10.w);  // (c,f,c)
-        f4 = make_float2(v11.x, v11.y);  // (c,c,f)
-        f0 = make_float2(v11.z, v11.w);  // (c,c,c)
     } else {
         // coordinates are >= 0: ceil = floor + (offset > 0), so the ceil corner's hash product is the floor corner's plus
         // 0 or the prime (mod 2^32) — two quarter-rate integer multiplies instead of four, no v_ceil / second convert
@@ -226,16 +230,18 @@ __device__ __forceinline__ float2 encode_level(const Grid &g, int l, float px, f
             f7 = t[(fx ^ hcy ^ hfz) & m];
         }
     }
+    // x stage: lerp of the (ceil, floor) pair, or, from the FAST dense element, fmaf(ox, d, e) with the difference already formed
+    auto lerp_x = [&](float a, float b) { return (DENSE && FAST) ? fmaf(ox, a, b) : lerp_t<FAST>(a, b, ox); };
     float2 r;
     {
-        const float f03 = lerp_t<FAST>(f0.x, f3.x, ox), f12 = lerp_t<FAST>(f1.x, f2.x, ox);
-        const float f56 = lerp_t<FAST>(f5.x, f6.x, ox), f47 = lerp_t<FAST>(f4.x, f7.x, ox);
+        const float f03 = lerp_x(f0.x, f3.x), f12 = lerp_x(f1.x, f2.x);
+        const float f56 = lerp_x(f5.x, f6.x), f47 = lerp_x(f4.x, f7.x);
         const float f0312 = lerp_t<FAST>(f03, f12, oy), f4756 = lerp_t<FAST>(f47, f56, oy);
         r.x = lerp_t<FAST>(f0312, f4756, oz);
     }
     {
-        const float f03 = lerp_t<FAST>(f0.y, f3.y, ox), f12 = lerp_t<FAST>(f1.y, f2.y, ox);
-        const float f56 = lerp_t<FAST>(f5.y, f6.y, ox), f47 = lerp_t<FAST>(f4.y, f7.y, ox);
+        const float f03 = lerp_x(f0.y, f3.y), f12 = lerp_x(f1.y, f2.y);
+        const float f56 = lerp_x(f5.y, f6.y), f47 = lerp_x(f4.y, f7.y);
         const float f0312 = lerp_t<FAST>(f03, f12, oy), f4756 = lerp_t<FAST>(f47, f56, oy);
         r.y = lerp_t<FAST>(f0312, f4756, oz);
     }
@@ -257,6 +263,7 @@ __device__ __forceinline__ float2 encode_level(const Grid &g, int l, float px, f
 struct HashTaps {
     unsigned off[8];  // byte offsets of the 8 corners inside the level's table, in the f0..f7 order of encode_level
     float ox, oy, oz;
+    bool dense;  // the corner array holds (entry, x-difference) pairs (dense_gather); a constant once the level loops are unrolled
 };
 template <typename G>
 __device__ __forceinline__ void hash_taps(const G &g, int l, float px, float py, float pz, HashTaps &t) {
@@ -265,6 +272,7 @@ __device__ __forceinline__ void hash_taps(const G &g, int l, float px, float py,
     t.ox = __builtin_amdgcn_fractf(sx);
     t.oy = __builtin_amdgcn_fractf(sy);
     t.oz = __builtin_amdgcn_fractf(sz);
+    t.dense = false;
     const unsigned fx = (unsigned)(int)sx, fy = (unsigned)(int)sy, fz = (unsigned)(int)sz;
     const unsigned x0 = fx << 3, x1 = x0 + 8u;
     const unsigned y0 = fy * (TN_P1 << 3), y1 = y0 + (TN_P1 << 3);
@@ -292,8 +300,10 @@ __device__ __forceinline__ void hash_gather(const G &g, int l, const HashTaps &t
 #endif
 constexpr int kFieldDense = TN_FIELD_DENSE_LEVELS;
 
-// The same two stages for a level of the DENSE re-layout (elements = aligned (entry(z), entry(z+1)) pairs): four byte offsets,
-// four 16-byte gathers, landing in the f0..f7 order of the hashed form.
+// The same two stages for a level of the DENSE re-layout (16-byte elements (e, d) = (entry, x-neighbour's entry - entry), see
+// tn_prepare.hip): two byte offsets, four 16-byte gathers from the x0 plane (the z+1 element is the next 16 bytes: an immediate).
+// In the corner array the slot of each x pair's floor corner (f3 f2 f6 f7) receives e and the slot of its ceil corner
+// (f0 f1 f5 f4) receives d, which is what hash_blend's x stage takes when t.dense is set.
 template <typename G>
 __device__ __forceinline__ void dense_taps(const G &g, int l, float px, float py, float pz, HashTaps &t) {
     const float s = g.scal[l];
@@ -301,23 +311,22 @@ __device__ __forceinline__ void dense_taps(const G &g, int l, float px, float py
     t.ox = __builtin_amdgcn_fractf(sx);
     t.oy = __builtin_amdgcn_fractf(sy);
     t.oz = __builtin_amdgcn_fractf(sz);
+    t.dense = true;
     const unsigned ures = (unsigned)g.dense_res[l];
     const unsigned i00 = __umul24(__umul24((unsigned)(int)sx, ures) + (unsigned)(int)sy, ures) + (unsigned)(int)sz;
-    const unsigned b00 = i00 << 4, dy = ures << 4, dx = __umul24(ures, ures) << 4;
-    t.off[0] = b00;            // (x0, y0): f6 | f2
-    t.off[1] = b00 + dy;       // (x0, y1): f7 | f3
-    t.off[2] = b00 + dx;       // (x1, y0): f5 | f1
-    t.off[3] = b00 + dx + dy;  // (x1, y1): f4 | f0
+    const unsigned b00 = i00 << 4, dy = ures << 4;
+    t.off[0] = b00;       // (x0, y0, z0): f6 | f5 - f6, and 16 bytes on (x0, y0, z1): f2 | f1 - f2
+    t.off[1] = b00 + dy;  // (x0, y1, z0): f7 | f4 - f7, and 16 bytes on (x0, y1, z1): f3 | f0 - f3
 }
 template <typename G>
 __device__ __forceinline__ void dense_gather(const G &g, int l, const HashTaps &t, float2 (&f)[8]) {
     const char *db = reinterpret_cast<const char *>(reinterpret_cast<const float4 *>(g.dense) + g.dense_off[l]);
-    const float4 v00 = *reinterpret_cast<const float4 *>(db + t.off[0]), v01 = *reinterpret_cast<const float4 *>(db + t.off[1]);
-    const float4 v10 = *reinterpret_cast<const float4 *>(db + t.off[2]), v11 = *reinterpret_cast<const float4 *>(db + t.off[3]);
-    f[6] = make_float2(v00.x, v00.y); f[2] = make_float2(v00.z, v00.w);
-    f[7] = make_float2(v01.x, v01.y); f[3] = make_float2(v01.z, v01.w);
-    f[5] = make_float2(v10.x, v10.y); f[1] = make_float2(v10.z, v10.w);
-    f[4] = make_float2(v11.x, v11.y); f[0] = make_float2(v11.z, v11.w);
+    const float4 v00 = *reinterpret_cast<const float4 *>(db + t.off[0]), v01 = *reinterpret_cast<const float4 *>(db + t.off[0] + 16);
+    const float4 v10 = *reinterpret_cast<const float4 *>(db + t.off[1]), v11 = *reinterpret_cast<const float4 *>(db + t.off[1] + 16);
+    f[6] = make_float2(v00.x, v00.y); f[5] = make_float2(v00.z, v00.w);
+    f[2] = make_float2(v01.x, v01.y); f[1] = make_float2(v01.z, v01.w);
+    f[7] = make_float2(v10.x, v10.y); f[4] = make_float2(v10.z, v10.w);
+    f[3] = make_float2(v11.x, v11.y); f[0] = make_float2(v11.z, v11.w);
 }
 // Pins the interpolation of a level BELOW the point where this is called: the interpolation weights pass through an opaque
 // asm, so the (pure) arithmetic that reads them cannot be placed earlier — without it instruction selection emits each
@@ -325,17 +334,19 @@ __device__ __forceinline__ void dense_gather(const G &g, int l, const HashTaps &
 __device__ __forceinline__ void hash_hold(HashTaps &t) {
     asm volatile("" : "+v"(t.ox), "+v"(t.oy), "+v"(t.oz)::"memory");
 }
+// t.dense: the x stage's differences came with the gather (dense_gather): one fma per pair in place of subtract + fma
 __device__ __forceinline__ float2 hash_blend(const HashTaps &t, const float2 (&f)[8]) {
+    auto lerp_x = [&](float a, float b) { return t.dense ? fmaf(t.ox, a, b) : lerp_t<true>(a, b, t.ox); };
     float2 r;
     {
-        const float f03 = lerp_t<true>(f[0].x, f[3].x, t.ox), f12 = lerp_t<true>(f[1].x, f[2].x, t.ox);
-        const float f56 = lerp_t<true>(f[5].x, f[6].x, t.ox), f47 = lerp_t<true>(f[4].x, f[7].x, t.ox);
+        const float f03 = lerp_x(f[0].x, f[3].x), f12 = lerp_x(f[1].x, f[2].x);
+        const float f56 = lerp_x(f[5].x, f[6].x), f47 = lerp_x(f[4].x, f[7].x);
         const float f0312 = lerp_t<true>(f03, f12, t.oy), f4756 = lerp_t<true>(f47, f56, t.oy);
         r.x = lerp_t<true>(f0312, f4756, t.oz);
     }
     {
-        const float f03 = lerp_t<true>(f[0].y, f[3].y, t.ox), f12 = lerp_t<true>(f[1].y, f[2].y, t.ox);
-        const float f56 = lerp_t<true>(f[5].y, f[6].y, t.ox), f47 = lerp_t<true>(f[4].y, f[7].y, t.ox);
+        const float f03 = lerp_x(f[0].y, f[3].y), f12 = lerp_x(f[1].y, f[2].y);
+        const float f56 = lerp_x(f[5].y, f[6].y), f47 = lerp_x(f[4].y, f[7].y);
         const float f0312 = lerp_t<true>(f03, f12, t.oy), f4756 = lerp_t<true>(f47, f56, t.oy);
         r.y = lerp_t<true>(f0312, f4756, t.oz);
     }
@@ -351,7 +362,8 @@ __device__ __forceinline__ float2 hash_blend(const HashTaps &t, const float2 (&f
 // GP > 0: s_setprio(GP) while a group's indices are computed and its gathers issued, s_setprio(0) for the interpolation (a caller's
 // A/B switch: the wave whose memory requests can go out ahead of its SIMD partners' arithmetic).
 // (hash_encode_pipelined_raw hands the level's taps and corner values to emit_raw(level - base, taps, corners): a caller that
-// wants more than the blended features — the training forward's position Jacobian — interpolates itself.)
+// wants more than the blended features — the training forward's position Jacobian — interpolates itself.  For a dense level
+// (taps.dense) the corner array holds (entry, x-difference) pairs, see dense_gather.)
 template <int NL, int LG, int ND = 0, int GP = 0, typename G, typename EmitRaw>
 __device__ __forceinline__ void hash_encode_pipelined_raw(const G &g, float px, float py, float pz, EmitRaw emit_raw, int base = 0) {
     static_assert(NL % LG == 0 && 16 * LG <= 64, "two groups of 8*LG gathers must fit the 6-bit vmcnt counter");
@@ -397,6 +409,7 @@ __device__ __forceinline__ void hash_encode_pipelined(const G &g, float px, floa
 }
 // hash_blend's features AND their derivatives with respect to the three interpolation offsets (jac[c] = d features / d offset c;
 // times the level's scale = d features / d normalised position).  The differences are the ones the lerps form anyway.
+// Hashed levels only (the training path never reads the dense re-layout).
 __device__ __forceinline__ float2 hash_blend_jac(const HashTaps &t, const float2 (&f)[8], float2 (&jac)[3]) {
     float2 r;
 #define TN_BLEND_JAC(c)                                                                                              \

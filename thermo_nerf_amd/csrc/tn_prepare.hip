@@ -2,7 +2,14 @@
 //
 // nerfstudio's torch HashEncoding hashes EVERY level, so a coarse level with (res+2)^3 <= T
 // vertices is scattered over T table slots (one vertex per cache line).  tn_hashgrid_prepare copies those
-// levels into dense[x][y][z] = table[hash(x,y,z)] (z fastest): same values, contiguous neighbours.
+// levels into a grid indexed [x][y][z] (z fastest) with contiguous neighbours.  With e(x,y,z) = table[hash(x,y,z)] a
+// 16-byte element holds
+//     dense[x][y][z] = (e(x,y,z), e(x+1,y,z) - e(x,y,z))
+// the entry and the difference to its x-neighbour, component-wise as ONE plain fp32 subtraction: exactly the `a - b` that
+// lerp_t<true>(a, b, o) = fmaf(o, a - b, b) rounds along x, formed here once per table version and not once per sample.  The
+// FAST readers take fmaf(ox, d, e) from four elements of the x0 plane (the z+1 element is the next 16 bytes); the torch-order
+// readers need the raw x+1 entry and read it as the base half of the element at x+1 (floor <= side - 2, so it exists).
+// The contents are a private layout between this file and tn_device.h: results are the hashed tables', bit for bit.
 #include "tn_device.h"
 
 namespace {
@@ -13,9 +20,11 @@ __global__ void dense_fill_kernel(const float2 *__restrict__ table, unsigned mas
         const unsigned z = (unsigned)(i % res);
         const unsigned y = (unsigned)((i / res) % res);
         const unsigned x = (unsigned)(i / ((long long)res * res));
-        // an entry and its z-neighbour as one aligned 16-byte piece (every entry is stored twice: no unaligned pair loads)
-        const float2 a = table[(x ^ (y * TN_P1) ^ (z * TN_P2)) & mask], b = table[(x ^ (y * TN_P1) ^ ((z + 1) * TN_P2)) & mask];
-        dense[i] = make_float4(a.x, a.y, b.x, b.y);
+        // an entry and the difference to its x-neighbour as one aligned 16-byte piece (the last x plane's neighbour is whatever
+        // the hash of x = side gives: coordinates keep floor <= side - 2, so no reader uses that difference)
+        const unsigned hyz = (y * TN_P1) ^ (z * TN_P2);
+        const float2 b = table[(x ^ hyz) & mask], a = table[((x + 1) ^ hyz) & mask];
+        dense[i] = make_float4(b.x, b.y, tn::sub_rn(a.x, b.x), tn::sub_rn(a.y, b.y));
     }
 }
 

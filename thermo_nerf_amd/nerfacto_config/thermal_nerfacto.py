@@ -76,8 +76,8 @@ class NerfactoModelConfig:
     positions only.  True = the behaviour of a differentiable (tcnn) SH encoding."""
     dense_grid_budget_mb: int = 64
     """>0: the proposal networks' eval kernels read their leading hash levels from a dense re-layout built within this budget
-    per network (dense[x][y][z] = (table[hash(x,y,z)], table[hash(x,y,z+1)]): layout only, bit-identical values; the two
-    z-corners of a cell are one aligned 16-byte load, so a level costs 4 gather instructions instead of 8).  64 MB holds 5
+    per network (dense[x][y][z] = (table[hash(x,y,z)], its x-neighbour's entry minus it): bit-identical results; an x pair
+    of corners is one aligned 16-byte load and its lerp one fma, so a level costs 4 gather instructions instead of 8).  64 MB holds 5
     and 4 of the reference's 2 x 5 proposal levels (45 + 41 MB); rebuilt when the tables change; never used in training."""
     field_dense_grid_budget_mb: int = 16
     """The same for the main field's 16-level grid: 16 MB holds the 6 levels (14.5 MB) the lane = ray field kernels read
