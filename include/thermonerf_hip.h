@@ -264,6 +264,50 @@ int tn_frame_to_rgb8(const float *src, int64_t num_pixels, int32_t channels, int
 int tn_otsu_thresholds(const uint8_t *pixels, const int64_t *offsets, int32_t num_images, uint32_t *histograms,
                        int32_t *thresholds, void *stream);
 
+/* Point-cloud export (what nerfstudio's point-cloud exporter does with rendered depth, plus a temperature per point): the
+ * per-ray outputs of a rendered pose -> the surviving points, appended in ray order behind a device-resident counter.
+ * Every step is one correctly rounded fp32 operation in the order and association written.  For ray i of num_rays:
+ *     p[c] = origins[i][c] + directions[i][c] * depth[i]                                   (multiply, add), c = 0..2
+ *     kept iff  accumulation[i] > min_accumulation
+ *          and  p[c] > box_min[c] and p[c] < box_max[c] for every c                        (on p, BEFORE to_world)
+ *          and  thermal[i] > thermal_lo and thermal[i] < thermal_hi
+ *   all comparisons strict; a NaN in depth, accumulation, thermal or p makes one false, so the ray is dropped; a bound of
+ *   -inf / +inf switches its test off.  For a kept ray, at index k = count_in + #{kept j < i} (count_in = count[0] as the call
+ *   finds it on the stream):
+ *     positions[k][c]   = ((M[c][0] * p[0] + M[c][1] * p[1]) + M[c][2] * p[2]) + M[c][3],  M = to_world, row-major 3 x 4
+ *     temperature[k]    = thermal[i] * temperature_span + temperature_min                  (degrees; span = max - min)
+ *     colors[k]         = TN_FRAME_SCALE of rgb[i]          (trunc(x * 255) saturated to [0, 255], NaN -> 0)
+ *     thermal_colors[k] = TN_FRAME_LUT of thermal[i] through thermal_table (uint8 [256, 3]), as tn_frame_to_rgb8 defines it
+ *     source[k]         = source_base + i
+ *   and count[0] = count_in + kept — the FULL number: nothing is written at an index >= capacity, and the host detects an
+ *   overflow as count > capacity after its one read-back.  thermal_colors (with its table) and source may be NULL.
+ * origins / directions / rgb [num_rays, 3], depth / accumulation / thermal [num_rays] device floats that may start at any
+ * ray of a larger allocation (4-byte alignment is all that is assumed); positions [capacity, 3] floats, colors /
+ * thermal_colors [capacity, 3] bytes, temperature [capacity] floats, source [capacity] int64, count 1 device int64.
+ * workspace: tn_pointcloud_workspace_bytes(num_rays) bytes of device scratch, 8-byte aligned (one int64 per tile).
+ * Three launches on `stream` (per-tile count, a one-block scan of the tile counts, emit), no host synchronisation, no
+ * allocation; the output order is a prefix sum and never depends on atomics, and no block waits for another.
+ * tn_pointcloud_tile_rays / tn_pointcloud_scan_width: rays per tile, and tile counts per pass of the scan block (the sizes at
+ * which the kernels change path; for tests).
+ * TN_ERR_NULL: a required pointer is NULL (the outputs are required when capacity > 0, the workspace when num_rays > 0);
+ * TN_ERR_SHAPE: num_rays or capacity negative, a float pointer not 4-byte aligned, count / source / workspace not 8-byte
+ * aligned; TN_ERR_WORKSPACE: workspace_bytes too small.  num_rays == 0: TN_OK, nothing is launched, count is untouched. */
+typedef struct tn_pointcloud_params {
+    float min_accumulation;
+    float box_min[3], box_max[3];
+    float thermal_lo, thermal_hi;
+    float temperature_span, temperature_min;
+    float to_world[12]; /* row-major 3 x 4 */
+} tn_pointcloud_params;
+int32_t tn_pointcloud_tile_rays(void);
+int32_t tn_pointcloud_scan_width(void);
+size_t tn_pointcloud_workspace_bytes(int64_t num_rays);
+int tn_pointcloud_append(const float *origins, const float *directions, const float *depth, const float *accumulation,
+                         const float *rgb, const float *thermal, int64_t num_rays, int64_t source_base,
+                         const tn_pointcloud_params *params, const uint8_t *thermal_table, float *positions, uint8_t *colors,
+                         float *temperature, uint8_t *thermal_colors, int64_t *source, int64_t capacity, int64_t *count,
+                         void *workspace, size_t workspace_bytes, void *stream);
+
 /* ------------------------------------------------------------------------------------------------------
  * Fused forward: Model.forward (collider) + ThermalNerfModel.get_outputs
  * [REF thermal_nerf_model.py:210-275]

@@ -76,6 +76,12 @@ class tn_space(C.Structure):
     ]
 
 
+class tn_pointcloud_params(C.Structure):
+    _fields_ = [("min_accumulation", C.c_float), ("box_min", C.c_float * 3), ("box_max", C.c_float * 3), ("thermal_lo", C.c_float),
+                ("thermal_hi", C.c_float), ("temperature_span", C.c_float), ("temperature_min", C.c_float),
+                ("to_world", C.c_float * 12)]
+
+
 class tn_density_field(C.Structure):
     _fields_ = [
         ("grid", tn_hashgrid),
@@ -209,6 +215,10 @@ SIGNATURES = {
     "tn_ssim_fwd": (C.c_int, [_vp, _vp, _i32, _i32, _i32, C.c_float, _vp, _sz, _vp, _vp]),
     "tn_frame_to_rgb8": (C.c_int, [_vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
     "tn_otsu_thresholds": (C.c_int, [_vp, C.POINTER(C.c_int64), _i32, _vp, _vp, _vp]),
+    "tn_pointcloud_tile_rays": (_i32, []),
+    "tn_pointcloud_scan_width": (_i32, []),
+    "tn_pointcloud_workspace_bytes": (_sz, [_i64]),
+    "tn_pointcloud_append": (C.c_int, [_vp] * 6 + [_i64, _i64, C.POINTER(tn_pointcloud_params)] + [_vp] * 6 + [_i64, _vp, _vp, _sz, _vp]),
     "tn_render_workspace_bytes": (_sz, [C.POINTER(tn_render_config), _i64]),
     "tn_render_rays_fwd": (
         C.c_int,

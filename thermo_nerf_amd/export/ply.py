@@ -1,0 +1,96 @@
+"""Binary little-endian PLY of a thermal point cloud: 19 bytes per vertex — ``float x y z``, ``uchar red green blue``,
+``float temperature`` (degrees Celsius).  Any cloud viewer opens it; the extra scalar shows up as a per-point property.
+
+The header is exactly (``M`` = the number of points, the bounds = the cloud's ``temperature_bounds`` as ``repr`` of two Python
+floats, or ``none none``)::
+
+    ply
+    format binary_little_endian 1.0
+    comment temperature_unit celsius
+    comment temperature_bounds MIN MAX
+    element vertex M
+    property float x
+    property float y
+    property float z
+    property uchar red
+    property uchar green
+    property uchar blue
+    property float temperature
+    end_header
+
+No time stamp, no host name: the same cloud gives the same bytes.
+"""
+from __future__ import annotations
+
+from pathlib import Path
+from typing import Dict
+
+import numpy as np
+
+VERTEX_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("red", "u1"), ("green", "u1"), ("blue", "u1"),
+                         ("temperature", "<f4")])
+assert VERTEX_DTYPE.itemsize == 19
+
+_PROPERTIES = ("property float x", "property float y", "property float z", "property uchar red", "property uchar green",
+               "property uchar blue", "property float temperature")
+
+
+def header(num_points: int, temperature_bounds=None) -> str:
+    lo, hi = (repr(float(v)) for v in temperature_bounds) if temperature_bounds is not None else ("none", "none")
+    lines = ["ply", "format binary_little_endian 1.0", "comment temperature_unit celsius", f"comment temperature_bounds {lo} {hi}",
+             f"element vertex {int(num_points)}", *_PROPERTIES, "end_header"]
+    return "\n".join(lines) + "\n"
+
+
+def _host(t) -> np.ndarray:
+    return t.detach().cpu().numpy() if hasattr(t, "detach") else np.asarray(t)
+
+
+def write_ply(path, cloud, colors: str = "rgb") -> Path:
+    """Write ``cloud`` (a ThermalPointCloud, on the device or the host) to ``path``.  ``colors``: which bytes fill red / green /
+    blue — "rgb" (the rendered colours) or "thermal" (the colour-mapped temperature).  One device -> host copy per array."""
+    if colors not in ("rgb", "thermal"):
+        raise ValueError('colors must be "rgb" or "thermal"')
+    col = cloud.colors if colors == "rgb" else cloud.thermal_colors
+    if col is None:
+        raise ValueError("the cloud holds no thermal colours (exported without a colour table)")
+    pos, col, temp = _host(cloud.positions), _host(col), _host(cloud.temperature)
+    m = pos.shape[0]
+    if pos.shape != (m, 3) or col.shape != (m, 3) or temp.shape != (m,):
+        raise ValueError("positions [M,3], colours [M,3] and temperature [M] must agree")
+    vertex = np.empty(m, dtype=VERTEX_DTYPE)
+    vertex["x"], vertex["y"], vertex["z"] = pos[:, 0], pos[:, 1], pos[:, 2]
+    vertex["red"], vertex["green"], vertex["blue"] = col[:, 0], col[:, 1], col[:, 2]
+    vertex["temperature"] = temp
+    path = Path(path)
+    path.parent.mkdir(parents=True, exist_ok=True)
+    with open(path, "wb") as f:
+        f.write(header(m, getattr(cloud, "temperature_bounds", None)).encode("ascii"))
+        vertex.tofile(f)
+    return path
+
+
+def read_ply(path) -> Dict:
+    """The arrays of a file ``write_ply`` wrote: ``positions`` float32 [M,3], ``colors`` uint8 [M,3], ``temperature`` float32 [M],
+    ``comments`` (the header's comment lines without the keyword).  M = 0 — a header without a body — is a valid file."""
+    blob = Path(path).read_bytes()
+    end = blob.find(b"end_header\n")
+    if not blob.startswith(b"ply\n") or end < 0:
+        raise ValueError(f"{path}: not a PLY file")
+    body = end + len(b"end_header\n")
+    lines = blob[:end].decode("ascii").split("\n")
+    if lines[1] != "format binary_little_endian 1.0":
+        raise ValueError(f"{path}: only binary little-endian PLY is read")
+    comments = [ln[len("comment "):] for ln in lines if ln.startswith("comment ")]
+    counts = [ln for ln in lines if ln.startswith("element ")]
+    if len(counts) != 1 or not counts[0].startswith("element vertex "):
+        raise ValueError(f"{path}: one vertex element expected")
+    if tuple(ln for ln in lines if ln.startswith("property ")) != _PROPERTIES:
+        raise ValueError(f"{path}: vertex properties differ from x y z red green blue temperature")
+    m = int(counts[0].split()[2])
+    if len(blob) - body != m * VERTEX_DTYPE.itemsize:
+        raise ValueError(f"{path}: {len(blob) - body} body bytes for {m} vertices of {VERTEX_DTYPE.itemsize} bytes")
+    vertex = np.frombuffer(blob, dtype=VERTEX_DTYPE, count=m, offset=body)
+    return {"positions": np.stack([vertex["x"], vertex["y"], vertex["z"]], axis=1) if m else np.zeros((0, 3), np.float32),
+            "colors": np.stack([vertex["red"], vertex["green"], vertex["blue"]], axis=1) if m else np.zeros((0, 3), np.uint8),
+            "temperature": vertex["temperature"].copy(), "comments": comments}
