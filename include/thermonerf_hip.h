@@ -308,6 +308,73 @@ int tn_pointcloud_append(const float *origins, const float *directions, const fl
                          float *temperature, uint8_t *thermal_colors, int64_t *source, int64_t capacity, int64_t *count,
                          void *workspace, size_t workspace_bytes, void *stream);
 
+/* Mesh export (what nerfstudio's TSDF exporter does with rendered depth, plus a temperature per vertex): rendered poses are
+ * fused into a voxel volume, and the volume becomes an indexed triangle list by SURFACE NETS — one vertex per sign-changing
+ * cell, one quad per sign-changing grid edge.  Every step is one correctly rounded fp32 operation in the order and association
+ * written, `/` and sqrt included.
+ *
+ * The volume: one contiguous float [7, Nz, Ny, Nx], zeroed by the caller; voxel (i, j, k) of a plane sits at (k Ny + j) Nx + i.
+ * Planes: 0 tsdf_sum, 1 weight, 2 thermal_sum, 3..5 r / g / b_sum, 6 colour_weight (weights are fp32 counts).  Grid point
+ * (i, j, k) is at p[c] = lo[c] + float(idx[c]) * step[c]; (Nx, Ny, Nz) = dims, every one >= 2 (TN_ERR_SHAPE otherwise) and
+ * Nx Ny Nz <= 2^31 - 1 (TN_ERR_UNSUPPORTED beyond: vertex indices are int32).
+ *
+ * tn_tsdf_integrate fuses ONE pose: depth / accumulation / thermal [height * width] and rgb [height * width, 3] device floats as
+ * RayRenderEngine.render leaves them (4-byte alignment is all that is assumed), a PINHOLE camera fx, fy, cx, cy and
+ * w2c = [R^T | -R^T t] (row-major 3 x 4) of its camera-to-world [R | t].  Per voxel, m = w2c:
+ *     q[r] = ((m[r][0] * p[0] + m[r][1] * p[1]) + m[r][2] * p[2]) + m[r][3],  r = 0..2
+ *     zc = -q[2]                                  (the camera looks along -z);  skipped unless zc > 0
+ *     u = (fx * q[0]) / zc + cx;   v = (fy * -q[1]) / zc + cy;   skipped unless 0 <= u < width and 0 <= v < height
+ *     pix = int(v) * width + int(u)               (the nearest pixel, centres at +0.5; never bilinear)
+ *     skipped unless accumulation[pix] > min_accumulation
+ *     dist = sqrt((q[0] * q[0] + q[1] * q[1]) + q[2] * q[2]);   sdf = depth[pix] - dist    (depth is a distance along the ray)
+ *     skipped unless sdf >= -truncation and sdf < +inf
+ *     tsdf_sum += min(1, sdf * inv_truncation);   weight += 1
+ *     if sdf <= truncation:  thermal_sum += thermal[pix];  r/g/b_sum += rgb[pix][c];  colour_weight += 1
+ *   A NaN makes a comparison false (skipped); a skipped voxel writes nothing.  One launch on `stream`, one thread per voxel.
+ *
+ * tn_mesh_extract.  A grid point is OBSERVED iff weight > 0, its value is f = tsdf_sum / weight, it is INSIDE iff observed
+ * and f < 0.  Cells are (Nx-1)(Ny-1)(Nz-1), x fastest; a cell is ACTIVE iff its 8 corners are all observed and neither all
+ * inside nor all outside.  A CROSSING edge: both ends observed, different insideness.
+ *   Vertices, one per active cell in ascending cell order; cell_index[cell] (the first int32 per cell of the workspace) = its
+ *   vertex index or -1, written for EVERY cell.  For cell (i, j, k), walk its 12 edges — axis a = 0, 1, 2, and within an axis the
+ *   offsets on the two other axes (ascending) run (0,0) (1,0) (0,1) (1,1) — with s[0..2] = 0, n = 0, and for each crossing edge
+ *   from corner A to B = A + e_a:   s[a] += f_A / (f_A - f_B);  s[other] += offset (0 or 1);  n += 1.  Then
+ *     local[c] = s[c] / n;   p[c] = lo[c] + (float(idx[c]) + local[c]) * step[c]
+ *     positions[k][c]   = ((M[c][0] * p[0] + M[c][1] * p[1]) + M[c][2] * p[2]) + M[c][3],  M = to_world
+ *   attributes: planes 2..6 each summed over the 8 corners from 0, x-fastest corner order; mean = sum / summed colour_weight;
+ *     temperature[k]    = mean_thermal * temperature_span + temperature_min
+ *     colors[k]         = TN_FRAME_SCALE of the mean rgb;  thermal_colors[k] = TN_FRAME_LUT of mean_thermal (may be NULL)
+ *   Triangles, in ascending (grid point, axis) order: for grid point p and axis a, with b = (a+1)%3, c = (a+2)%3, the edge
+ *   p -> p + e_a gives a quad iff it is crossing and the four cells at offsets (-1,-1) (0,-1) (0,0) (-1,0) in (b, c) from p's own
+ *   cell coordinates all exist and are active; v0..v3 = their cell_index in that order, reversed to v0 v3 v2 v1 when p + e_a is
+ *   the inside end (normals point from inside to outside); two triangles (v0 v1 v2), (v0 v2 v3).
+ *   counts[0], counts[1] (device int64) are OVERWRITTEN with the full numbers of vertices and triangles; vertex data is written
+ *   only below capacity_vertices, triangles only below capacity_triangles (both 0 with NULL outputs: the sizing call).
+ * positions [capacity_vertices, 3] floats, colors / thermal_colors [., 3] bytes, temperature floats, triangles
+ * [capacity_triangles, 3] int32.  workspace: tn_mesh_workspace_bytes(Nx, Ny, Nz) bytes, 8-byte aligned.  Six launches on
+ * `stream` (count, one-block scan, emit; twice), no atomics, no host synchronisation, no allocation; no block waits for another.
+ * tn_mesh_tile / tn_mesh_scan_width: cells or grid points per tile, tile counts per pass of the scan block (for tests).
+ * TN_ERR_NULL: a required pointer is NULL (outputs are required when their capacity > 0, the table with thermal_colors);
+ * TN_ERR_SHAPE: a dim < 2, height or width < 1, a negative capacity, a misaligned pointer; TN_ERR_WORKSPACE: workspace_bytes
+ * too small.  All are returned before any launch. */
+typedef struct tn_mesh_params {
+    float fx, fy, cx, cy;
+    float w2c[12]; /* row-major 3 x 4 */
+    float truncation, inv_truncation, min_accumulation;
+    float lo[3], step[3];
+    int32_t dims[3]; /* Nx, Ny, Nz */
+    float temperature_span, temperature_min;
+    float to_world[12]; /* row-major 3 x 4 */
+} tn_mesh_params;
+int32_t tn_mesh_tile(void);
+int32_t tn_mesh_scan_width(void);
+size_t tn_mesh_workspace_bytes(int32_t nx, int32_t ny, int32_t nz);
+int tn_tsdf_integrate(const float *depth, const float *accumulation, const float *thermal, const float *rgb, int32_t height,
+                      int32_t width, const tn_mesh_params *params, float *volume, void *stream);
+int tn_mesh_extract(const float *volume, const tn_mesh_params *params, const uint8_t *thermal_table, float *positions,
+                    uint8_t *colors, float *temperature, uint8_t *thermal_colors, int64_t capacity_vertices, int32_t *triangles,
+                    int64_t capacity_triangles, int64_t *counts, void *workspace, size_t workspace_bytes, void *stream);
+
 /* ------------------------------------------------------------------------------------------------------
  * Fused forward: Model.forward (collider) + ThermalNerfModel.get_outputs
  * [REF thermal_nerf_model.py:210-275]

@@ -82,6 +82,13 @@ class tn_pointcloud_params(C.Structure):
                 ("to_world", C.c_float * 12)]
 
 
+class tn_mesh_params(C.Structure):
+    _fields_ = [("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("w2c", C.c_float * 12),
+                ("truncation", C.c_float), ("inv_truncation", C.c_float), ("min_accumulation", C.c_float), ("lo", C.c_float * 3),
+                ("step", C.c_float * 3), ("dims", C.c_int32 * 3), ("temperature_span", C.c_float), ("temperature_min", C.c_float),
+                ("to_world", C.c_float * 12)]
+
+
 class tn_density_field(C.Structure):
     _fields_ = [
         ("grid", tn_hashgrid),
@@ -219,6 +226,11 @@ SIGNATURES = {
     "tn_pointcloud_scan_width": (_i32, []),
     "tn_pointcloud_workspace_bytes": (_sz, [_i64]),
     "tn_pointcloud_append": (C.c_int, [_vp] * 6 + [_i64, _i64, C.POINTER(tn_pointcloud_params)] + [_vp] * 6 + [_i64, _vp, _vp, _sz, _vp]),
+    "tn_mesh_tile": (_i32, []),
+    "tn_mesh_scan_width": (_i32, []),
+    "tn_mesh_workspace_bytes": (_sz, [_i32, _i32, _i32]),
+    "tn_tsdf_integrate": (C.c_int, [_vp] * 4 + [_i32, _i32, C.POINTER(tn_mesh_params), _vp, _vp]),
+    "tn_mesh_extract": (C.c_int, [_vp, C.POINTER(tn_mesh_params)] + [_vp] * 5 + [_i64, _vp, _i64, _vp, _vp, _sz, _vp]),
     "tn_render_workspace_bytes": (_sz, [C.POINTER(tn_render_config), _i64]),
     "tn_render_rays_fwd": (
         C.c_int,

@@ -19,6 +19,7 @@
 // that count a few tens of microseconds per 1080p pose beside a ~30 ms render (an estimate from the bytes, not a measurement:
 // tools/export_bench.py).  Like tn_frame.hip the kernels are launch- and latency-bound and not a tuning target.
 #include "tn_device.h"
+#include "tn_scan.h"
 
 using namespace tn;
 
@@ -26,8 +27,6 @@ namespace {
 
 constexpr int kTile = 256;    // rays per tile = threads per block of the count and emit kernels
 constexpr int kWaves = kTile / TN_WAVE;
-constexpr int kScan = 1024;   // tile counts the scan block takes per pass = its threads
-constexpr int kScanWaves = kScan / TN_WAVE;
 
 struct Ray {  // what the predicate leaves behind for the emit
     float p[3];
@@ -74,35 +73,7 @@ count_kernel(const float *__restrict__ origins, const float *__restrict__ direct
 
 __global__ void __launch_bounds__(kScan)
 scan_kernel(long long *__restrict__ tiles, long long num_tiles, long long *__restrict__ count) {
-    __shared__ uint32_t wave_total[kScanWaves];
-    __shared__ long long count_in;
-    const int lane = threadIdx.x % TN_WAVE, wave = threadIdx.x / TN_WAVE;
-    if (threadIdx.x == 0) count_in = count[0];  // (the one thread that writes it back reads it)
-    __syncthreads();
-    long long carry = count_in;
-    for (long long first = 0; first < num_tiles; first += kScan) {
-        const long long b = first + threadIdx.x;
-        const uint32_t own = b < num_tiles ? (uint32_t)tiles[b] : 0u;
-        uint32_t incl = own;  // a pass sums at most kScan * kTile = 2^18
-#pragma unroll
-        for (int o = 1; o < TN_WAVE; o <<= 1) {
-            const uint32_t up = __shfl_up(incl, o, TN_WAVE);
-            if (lane >= o) incl += up;
-        }
-        if (lane == TN_WAVE - 1) wave_total[wave] = incl;
-        __syncthreads();
-        uint32_t before = 0, total = 0;
-#pragma unroll
-        for (int w = 0; w < kScanWaves; ++w) {
-            const uint32_t v = wave_total[w];
-            before += w < wave ? v : 0u;
-            total += v;
-        }
-        if (b < num_tiles) tiles[b] = carry + (long long)(before + incl - own);
-        carry += (long long)total;
-        __syncthreads();  // wave_total is rewritten by the next pass
-    }
-    if (threadIdx.x == 0) count[0] = carry;
+    scan_tiles<true>(tiles, num_tiles, count);  // a pass sums at most kScan * kTile = 2^18
 }
 
 __global__ void __launch_bounds__(kTile)

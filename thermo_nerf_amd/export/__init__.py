@@ -1,4 +1,7 @@
-"""Export of a trained scene as 3-D data: a thermal point cloud (positions, colours, degrees per point) and its PLY file."""
-from .ply import read_ply, write_ply  # noqa: F401
+"""Export of a trained scene as 3-D data: a thermal point cloud (positions, colours, degrees per point), a thermal
+triangle mesh (TSDF fusion + surface nets, degrees per vertex) and their PLY files."""
+from .mesh import (MeshExporter, ThermalMesh, camera_pose, grid_dims, mesh_extract, mesh_params, mesh_scan_width,  # noqa: F401
+                   mesh_tile, mesh_workspace_bytes, set_camera, tsdf_integrate, world_to_camera)
+from .ply import read_mesh_ply, read_ply, write_mesh_ply, write_ply  # noqa: F401
 from .pointcloud import (PointCloudExporter, ThermalPointCloud, pointcloud_append, pointcloud_params, scan_width,  # noqa: F401
                          subsample, subsample_indices, tile_rays, workspace_bytes, world_transform)

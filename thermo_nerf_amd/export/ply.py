@@ -94,3 +94,75 @@ def read_ply(path) -> Dict:
     return {"positions": np.stack([vertex["x"], vertex["y"], vertex["z"]], axis=1) if m else np.zeros((0, 3), np.float32),
             "colors": np.stack([vertex["red"], vertex["green"], vertex["blue"]], axis=1) if m else np.zeros((0, 3), np.uint8),
             "temperature": vertex["temperature"].copy(), "comments": comments}
+
+
+# ---- triangle meshes ---------------------------------------------------------------------------------------------------------------
+# The cloud's header up to its last vertex property, then ``element face T`` / ``property list uchar int vertex_indices``: 19 bytes per
+# vertex, 13 per face (the count byte 3 and three little-endian int32).  The same determinism: the same mesh gives the same bytes.
+FACE_DTYPE = np.dtype([("n", "u1"), ("v", "<i4", (3,))])
+assert FACE_DTYPE.itemsize == 13
+
+_FACE_LINES = ("property list uchar int vertex_indices",)
+
+
+def mesh_header(num_vertices: int, num_triangles: int, temperature_bounds=None) -> str:
+    lines = header(num_vertices, temperature_bounds).split("\n")[:-2]  # without end_header
+    return "\n".join(lines + [f"element face {int(num_triangles)}", *_FACE_LINES, "end_header"]) + "\n"
+
+
+def write_mesh_ply(path, mesh, colors: str = "rgb") -> Path:
+    """Write ``mesh`` (a ThermalMesh, on the device or the host) to ``path``; ``colors`` as in ``write_ply``.  V = 0 or T = 0 is a
+    valid file.  One device -> host copy per array."""
+    if colors not in ("rgb", "thermal"):
+        raise ValueError('colors must be "rgb" or "thermal"')
+    col = mesh.colors if colors == "rgb" else mesh.thermal_colors
+    if col is None:
+        raise ValueError("the mesh holds no thermal colours (extracted without a colour table)")
+    pos, col, temp, tri = _host(mesh.positions), _host(col), _host(mesh.temperature), _host(mesh.triangles)
+    m, t = pos.shape[0], tri.shape[0]
+    if pos.shape != (m, 3) or col.shape != (m, 3) or temp.shape != (m,) or tri.shape != (t, 3):
+        raise ValueError("positions [V,3], colours [V,3], temperature [V] and triangles [T,3] must agree")
+    if t and (tri.min() < 0 or tri.max() >= m):
+        raise ValueError("a triangle names a vertex outside [0, V)")
+    vertex = np.empty(m, dtype=VERTEX_DTYPE)
+    vertex["x"], vertex["y"], vertex["z"] = pos[:, 0], pos[:, 1], pos[:, 2]
+    vertex["red"], vertex["green"], vertex["blue"] = col[:, 0], col[:, 1], col[:, 2]
+    vertex["temperature"] = temp
+    face = np.empty(t, dtype=FACE_DTYPE)
+    face["n"], face["v"] = 3, tri
+    path = Path(path)
+    path.parent.mkdir(parents=True, exist_ok=True)
+    with open(path, "wb") as f:
+        f.write(mesh_header(m, t, getattr(mesh, "temperature_bounds", None)).encode("ascii"))
+        vertex.tofile(f)
+        face.tofile(f)
+    return path
+
+
+def read_mesh_ply(path) -> Dict:
+    """The arrays of a file ``write_mesh_ply`` wrote: ``read_ply``'s ``positions`` / ``colors`` / ``temperature`` / ``comments`` and
+    ``triangles`` int32 [T,3]."""
+    blob = Path(path).read_bytes()
+    end = blob.find(b"end_header\n")
+    if not blob.startswith(b"ply\n") or end < 0:
+        raise ValueError(f"{path}: not a PLY file")
+    body = end + len(b"end_header\n")
+    lines = blob[:end].decode("ascii").split("\n")
+    if lines[1] != "format binary_little_endian 1.0":
+        raise ValueError(f"{path}: only binary little-endian PLY is read")
+    counts = [ln.split() for ln in lines if ln.startswith("element ")]
+    if [c[1] for c in counts] != ["vertex", "face"]:
+        raise ValueError(f"{path}: a vertex element and a face element expected")
+    if tuple(ln for ln in lines if ln.startswith("property ")) != _PROPERTIES + _FACE_LINES:
+        raise ValueError(f"{path}: properties differ from x y z red green blue temperature / vertex_indices")
+    m, t = int(counts[0][2]), int(counts[1][2])
+    if len(blob) - body != m * VERTEX_DTYPE.itemsize + t * FACE_DTYPE.itemsize:
+        raise ValueError(f"{path}: {len(blob) - body} body bytes for {m} vertices and {t} faces")
+    vertex = np.frombuffer(blob, dtype=VERTEX_DTYPE, count=m, offset=body)
+    face = np.frombuffer(blob, dtype=FACE_DTYPE, count=t, offset=body + m * VERTEX_DTYPE.itemsize)
+    if t and not (face["n"] == 3).all():
+        raise ValueError(f"{path}: only triangles are read")
+    return {"positions": np.stack([vertex["x"], vertex["y"], vertex["z"]], axis=1) if m else np.zeros((0, 3), np.float32),
+            "colors": np.stack([vertex["red"], vertex["green"], vertex["blue"]], axis=1) if m else np.zeros((0, 3), np.uint8),
+            "temperature": vertex["temperature"].copy(), "triangles": face["v"].astype(np.int32).reshape(t, 3),
+            "comments": [ln[len("comment "):] for ln in lines if ln.startswith("comment ")]}

@@ -1,0 +1,101 @@
+#!/usr/bin/env python
+"""Export a finished run as a thermal triangle mesh: a binary PLY with a position, a colour and a temperature in degrees Celsius per vertex.
+
+    python tools/export_mesh.py RUN_DIR DATASET --output mesh.ply --resolution 256 --colors thermal
+
+RUN_DIR is a run directory of tools/train_eval.py (``config.json``: model settings, number of training cameras, temperature
+bounds; ``--config-json`` overrides model fields; the newest ``step-*.ckpt``: the weights).  Every camera of the chosen split of
+DATASET is rendered as a pinhole view and its depth fused into a voxel volume over the bounding box (the dataset's scene box
+unless ``--bounding-box-min/-max``): ``--resolution`` grid points along the longest side (or three numbers), a truncation band of
+``--truncation`` scene units (default: 4 grid steps); pixels at or below ``--min-accumulation`` observe nothing.  The surface is
+extracted by surface nets; a vertex carries the mean colour and temperature of the near-surface observations around it.
+Training cameras are rendered with their optimised poses.
+
+Positions are written in the dataset's original world frame; ``--scene-frame`` keeps the normalised frame the model was trained in.
+"""
+from __future__ import annotations
+
+import argparse
+import os
+import sys
+from pathlib import Path
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+
+def parse(argv=None) -> argparse.Namespace:
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("model_uri", type=Path, help="run directory of the model")
+    ap.add_argument("dataset_path", type=Path, help="dataset directory or its transforms.json")
+    ap.add_argument("--output", type=Path, required=True, help="the PLY file to write")
+    ap.add_argument("--split", choices=("train", "val"), default="train", help="which cameras of the dataset to fuse")
+    ap.add_argument("--resolution", type=int, nargs="+", default=[256], metavar="N",
+                    help="grid points along the longest side of the box, or three numbers NX NY NZ")
+    ap.add_argument("--truncation", type=float, default=None, help="the TSDF band in scene units (default: 4 grid steps)")
+    ap.add_argument("--resolution-scale", type=float, default=1.0, help="scale of the rendered resolution")
+    ap.add_argument("--depth", choices=("depth", "expected_depth"), default="depth",
+                    help="the depth output to fuse (expected_depth depends on the eval chunk size)")
+    ap.add_argument("--min-accumulation", type=float, default=0.5, help="pixels at or below this opacity observe nothing")
+    ap.add_argument("--bounding-box-min", type=float, nargs=3, default=None, metavar=("X", "Y", "Z"))
+    ap.add_argument("--bounding-box-max", type=float, nargs=3, default=None, metavar=("X", "Y", "Z"))
+    ap.add_argument("--colors", choices=("rgb", "thermal"), default="rgb", help="what fills red / green / blue")
+    ap.add_argument("--scene-frame", action="store_true", help="write the normalised scene frame, not the dataset's world frame")
+    ap.add_argument("--config-json", type=Path, default=None, help="model fields that override the run's config.json")
+    ap.add_argument("--device", default="cuda")
+    args = ap.parse_args(argv)
+    if (args.bounding_box_min is None) != (args.bounding_box_max is None):
+        ap.error("--bounding-box-min and --bounding-box-max go together")
+    if len(args.resolution) not in (1, 3) or min(args.resolution) < 2:
+        ap.error("--resolution takes one number or three, each at least 2")
+    return args
+
+
+def build_exporter(args):
+    """(exporter, cameras of the split, apply_camera_optimizer) as ``main`` sets them up — also what a caller that wants the mesh
+    in-process uses"""
+    from thermo_nerf_amd import run_config
+    from thermo_nerf_amd.data import ThermalDataParserConfig
+    from thermo_nerf_amd.export import MeshExporter, world_transform
+    from thermo_nerf_amd.render import Renderer
+
+    run = run_config.read_run_config(args.model_uri)
+    over = dict(run.get("model", {}))
+    over.update(run_config.load_overrides(args.config_json))
+    config = run_config.model_config(over)
+    parsed = ThermalDataParserConfig(data=Path(args.dataset_path), eval_mode=run.get("eval_mode", "filename")).setup() \
+        .get_dataparser_outputs(args.split)
+    renderer = Renderer.from_checkpoint(args.model_uri, config, int(run["num_train_data"]), device=args.device,
+                                        scene_box=parsed.scene_box)
+    cameras = parsed.cameras
+    if args.resolution_scale != 1.0:
+        cameras.rescale_output_resolution(args.resolution_scale)
+    max_t, min_t = (float(v) for v in run["temperature_bounds"])
+    box = [args.bounding_box_min, args.bounding_box_max] if args.bounding_box_min is not None else parsed.scene_box.aabb
+    resolution = args.resolution[0] if len(args.resolution) == 1 else tuple(args.resolution)
+    exporter = MeshExporter(renderer.model, max_temperature=max_t, min_temperature=min_t, resolution=resolution, bounding_box=box,
+                            truncation=args.truncation, min_accumulation=args.min_accumulation, depth_output_name=args.depth,
+                            to_world=None if args.scene_frame else world_transform(parsed))
+    return exporter, cameras, args.split == "train"
+
+
+def main(argv=None) -> int:
+    args = parse(argv)
+    from thermo_nerf_amd.export import write_mesh_ply
+
+    exporter, cameras, adjust = build_exporter(args)
+    mesh = exporter.export(cameras, apply_camera_optimizer=adjust)
+    write_mesh_ply(args.output, mesh, colors=args.colors)
+    nx, ny, nz = exporter.dims
+    print(f"poses fused {exporter.last_poses} into {nx} x {ny} x {nz}, vertices {len(mesh)}, triangles {int(mesh.triangles.shape[0])} "
+          f"-> {args.output}")
+    if len(mesh):
+        print(f"temperature min {float(mesh.temperature.min()):.3f} C, max {float(mesh.temperature.max()):.3f} C")
+    else:
+        print("temperature min -, max - (no surface inside the box)")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
