@@ -308,7 +308,47 @@ int tn_pointcloud_append(const float *origins, const float *directions, const fl
                          float *temperature, uint8_t *thermal_colors, int64_t *source, int64_t capacity, int64_t *count,
                          void *workspace, size_t workspace_bytes, void *stream);
 
-/* Mesh export (what nerfstudio's TSDF exporter does with rendered depth, plus a temperature per vertex): rendered poses are
+/* k nearest neighbours of every point of a cloud (what the exporter's outlier removal and normals are built on).  The list
+ * of (d2, index) pairs of a point is defined bit for bit.  positions: [num_points, 3] device floats; a point is FINITE iff
+ * its three coordinates are.  For finite points i != j, every step ONE correctly rounded fp32 operation:
+ *     dx = x_i - x_j,  dy = y_i - y_j,  dz = z_i - z_j;     d2 = (dx * dx + dy * dy) + dz * dz
+ * The neighbours of i are the k other finite points with the smallest (d2, j) in lexicographic order: a tie in d2 goes to
+ * the lower index.  A point is never its own neighbour; a duplicate at the same position is one, with d2 = 0.  Row i of
+ * neighbor_index (int32 [num_points, k]) and neighbor_d2 (float [num_points, k]) holds them in ascending (d2, j) order;
+ * where fewer than k other finite points exist the remaining slots hold -1 and +inf.  A non-finite point is nobody's
+ * neighbour and its own row is all -1 and +inf.  mean_distance (double [num_points]): for a finite point with a full row
+ *     (sqrt((double)d2_0) + sqrt((double)d2_1) + ... ) / k       summed in fp64 from 0 in row order,
+ * +inf for every other point.  Any of the three outputs may be NULL.
+ * grid_resolution: the number of cells, along the longest side of the finite points' bounding box, of the uniform grid
+ * that makes the search local: 0 lets the library choose from num_points (tn_knn_grid_resolution tells what it chooses),
+ * 1 .. 512 forces it.  THE OUTPUTS DO NOT DEPEND ON IT: the search leaves a shell of cells only when the list is full and
+ * its worst d2 is strictly below a lower bound, valid for the COMPUTED fp32 d2, on anything it has not seen
+ * (thermo_nerf_amd/csrc/tn_knn.hip and DESIGN.md state the argument).  An isolated point costs many empty shells.
+ * workspace: tn_knn_workspace_bytes(num_points, grid_resolution) device bytes, 16-byte aligned.  Eight launches and one
+ * memset on `stream`, no host synchronisation, no allocation.  Points are counted into cells with integer atomic adds; no
+ * block waits for another, and nothing in the outputs depends on the order of arrival.
+ * TN_ERR_UNSUPPORTED: k < 1 or k > 32; TN_ERR_SHAPE: num_points < 0 or > 2^31 - 1, grid_resolution < 0 or > 512, a
+ * misaligned pointer; num_points == 0: TN_OK, nothing is launched or written; then TN_ERR_NULL: positions or workspace is
+ * NULL; TN_ERR_WORKSPACE: workspace_bytes too small.  All are returned before any launch.
+ *
+ * tn_pointcloud_normals: a normal per point from its neighbour rows.  Point i's neighbourhood is i itself followed by the
+ * valid entries (0 <= j < num_points) of row i of neighbor_index, in row order.  A non-finite point, or one with fewer than 2
+ * valid neighbours, gets (0, 0, 0).  Otherwise, in fp64, every step one correctly rounded operation, summed from 0 in
+ * neighbourhood order:  c = (sum of q) / count;  C[a][b] = sum of (q_a - c_a) * (q_b - c_b)  — the covariance, defined bit
+ * for bit.  The normal is the unit eigenvector of C's smallest eigenvalue (cyclic Jacobi in fp64; the eigenvector is
+ * defined to a tolerance, not to the bit), rounded once to fp32.  Sign, with viewpoints [num_points, 3] floats or NULL:
+ * s = sum over c of n_c * (v_c - p_c) in fp64; the normal is negated iff s < 0; if s == 0, the viewpoint is non-finite or
+ * viewpoints is NULL, the component of largest |n_c| (the lowest c on a tie) is made positive.  One launch.
+ * TN_ERR_UNSUPPORTED: k < 1 or k > 32; TN_ERR_SHAPE: num_points out of range, a misaligned pointer; num_points == 0: TN_OK;
+ * TN_ERR_NULL: positions, neighbor_index or normals is NULL. */
+int32_t tn_knn_grid_resolution(int64_t num_points);
+size_t tn_knn_workspace_bytes(int64_t num_points, int32_t grid_resolution);
+int tn_knn(const float *positions, int64_t num_points, int32_t k, int32_t grid_resolution, int32_t *neighbor_index,
+           float *neighbor_d2, double *mean_distance, void *workspace, size_t workspace_bytes, void *stream);
+int tn_pointcloud_normals(const float *positions, const int32_t *neighbor_index, int64_t num_points, int32_t k,
+                          const float *viewpoints, float *normals, void *stream);
+
+/* Mesh export(what nerfstudio's TSDF exporter does with rendered depth, plus a temperature per vertex): rendered poses are
  * fused into a voxel volume, and the volume becomes an indexed triangle list by SURFACE NETS — one vertex per sign-changing
  * cell, one quad per sign-changing grid edge.  Every step is one correctly rounded fp32 operation in the order and association
  * written, `/` and sqrt included.

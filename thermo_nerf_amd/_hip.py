@@ -226,6 +226,10 @@ SIGNATURES = {
     "tn_pointcloud_scan_width": (_i32, []),
     "tn_pointcloud_workspace_bytes": (_sz, [_i64]),
     "tn_pointcloud_append": (C.c_int, [_vp] * 6 + [_i64, _i64, C.POINTER(tn_pointcloud_params)] + [_vp] * 6 + [_i64, _vp, _vp, _sz, _vp]),
+    "tn_knn_grid_resolution": (_i32, [_i64]),
+    "tn_knn_workspace_bytes": (_sz, [_i64, _i32]),
+    "tn_knn": (C.c_int, [_vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "tn_pointcloud_normals": (C.c_int, [_vp, _vp, _i64, _i32, _vp, _vp, _vp]),
     "tn_mesh_tile": (_i32, []),
     "tn_mesh_scan_width": (_i32, []),
     "tn_mesh_workspace_bytes": (_sz, [_i32, _i32, _i32]),

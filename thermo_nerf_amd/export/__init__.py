@@ -1,7 +1,9 @@
-"""Export of a trained scene as 3-D data: a thermal point cloud (positions, colours, degrees per point), a thermal
-triangle mesh (TSDF fusion + surface nets, degrees per vertex) and their PLY files."""
+"""Export of a trained scene as 3-D data: a thermal point cloud (positions, colours, degrees per point; optionally without
+statistical outliers and with normals, both from a k-nearest-neighbour search on the device), a thermal triangle mesh (TSDF fusion + surface nets, degrees per vertex) and their PLY files."""
 from .mesh import (MeshExporter, ThermalMesh, camera_pose, grid_dims, mesh_extract, mesh_params, mesh_scan_width,  # noqa: F401
                    mesh_tile, mesh_workspace_bytes, set_camera, tsdf_integrate, world_to_camera)
+from .neighbors import (Neighbors, estimate_normals, knn, knn_grid_resolution, knn_workspace_bytes, outlier_keep_mask,  # noqa: F401
+                        pointcloud_normals, remove_statistical_outliers)
 from .ply import read_mesh_ply, read_ply, write_mesh_ply, write_ply  # noqa: F401
 from .pointcloud import (PointCloudExporter, ThermalPointCloud, pointcloud_append, pointcloud_params, scan_width,  # noqa: F401
                          subsample, subsample_indices, tile_rays, workspace_bytes, world_transform)

@@ -19,6 +19,9 @@ floats, or ``none none``)::
     end_header
 
 No time stamp, no host name: the same cloud gives the same bytes.
+
+A cloud that carries normals (``estimate_normals``) is written with ``property float nx`` / ``ny`` / ``nz`` between ``z`` and
+``red``: 31 bytes per vertex, the layout cloud viewers and Poisson reconstruction expect.  Without normals the file is the one above.
 """
 from __future__ import annotations
 
@@ -34,11 +37,17 @@ assert VERTEX_DTYPE.itemsize == 19
 _PROPERTIES = ("property float x", "property float y", "property float z", "property uchar red", "property uchar green",
                "property uchar blue", "property float temperature")
 
+NORMAL_VERTEX_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4"), ("red", "u1"),
+                                ("green", "u1"), ("blue", "u1"), ("temperature", "<f4")])
+assert NORMAL_VERTEX_DTYPE.itemsize == 31
 
-def header(num_points: int, temperature_bounds=None) -> str:
+_NORMAL_PROPERTIES = _PROPERTIES[:3] + ("property float nx", "property float ny", "property float nz") + _PROPERTIES[3:]
+
+
+def header(num_points: int, temperature_bounds=None, normals: bool = False) -> str:
     lo, hi = (repr(float(v)) for v in temperature_bounds) if temperature_bounds is not None else ("none", "none")
     lines = ["ply", "format binary_little_endian 1.0", "comment temperature_unit celsius", f"comment temperature_bounds {lo} {hi}",
-             f"element vertex {int(num_points)}", *_PROPERTIES, "end_header"]
+             f"element vertex {int(num_points)}", *(_NORMAL_PROPERTIES if normals else _PROPERTIES), "end_header"]
     return "\n".join(lines) + "\n"
 
 
@@ -48,7 +57,8 @@ def _host(t) -> np.ndarray:
 
 def write_ply(path, cloud, colors: str = "rgb") -> Path:
     """Write ``cloud`` (a ThermalPointCloud, on the device or the host) to ``path``.  ``colors``: which bytes fill red / green /
-    blue — "rgb" (the rendered colours) or "thermal" (the colour-mapped temperature).  One device -> host copy per array."""
+    blue — "rgb" (the rendered colours) or "thermal" (the colour-mapped temperature).  ``cloud.normals``, where set, are written
+    as nx ny nz behind z.  One device -> host copy per array."""
     if colors not in ("rgb", "thermal"):
         raise ValueError('colors must be "rgb" or "thermal"')
     col = cloud.colors if colors == "rgb" else cloud.thermal_colors
@@ -58,21 +68,28 @@ def write_ply(path, cloud, colors: str = "rgb") -> Path:
     m = pos.shape[0]
     if pos.shape != (m, 3) or col.shape != (m, 3) or temp.shape != (m,):
         raise ValueError("positions [M,3], colours [M,3] and temperature [M] must agree")
-    vertex = np.empty(m, dtype=VERTEX_DTYPE)
+    normals = getattr(cloud, "normals", None)
+    vertex = np.empty(m, dtype=VERTEX_DTYPE if normals is None else NORMAL_VERTEX_DTYPE)
     vertex["x"], vertex["y"], vertex["z"] = pos[:, 0], pos[:, 1], pos[:, 2]
     vertex["red"], vertex["green"], vertex["blue"] = col[:, 0], col[:, 1], col[:, 2]
     vertex["temperature"] = temp
+    if normals is not None:
+        nrm = _host(normals)
+        if nrm.shape != (m, 3):
+            raise ValueError("normals must be [M,3]")
+        vertex["nx"], vertex["ny"], vertex["nz"] = nrm[:, 0], nrm[:, 1], nrm[:, 2]
     path = Path(path)
     path.parent.mkdir(parents=True, exist_ok=True)
     with open(path, "wb") as f:
-        f.write(header(m, getattr(cloud, "temperature_bounds", None)).encode("ascii"))
+        f.write(header(m, getattr(cloud, "temperature_bounds", None), normals is not None).encode("ascii"))
         vertex.tofile(f)
     return path
 
 
 def read_ply(path) -> Dict:
     """The arrays of a file ``write_ply`` wrote: ``positions`` float32 [M,3], ``colors`` uint8 [M,3], ``temperature`` float32 [M],
-    ``comments`` (the header's comment lines without the keyword).  M = 0 — a header without a body — is a valid file."""
+    ``comments`` (the header's comment lines without the keyword), and ``normals`` float32 [M,3] when the file carries them (the
+    31-byte layout).  M = 0 — a header without a body — is a valid file."""
     blob = Path(path).read_bytes()
     end = blob.find(b"end_header\n")
     if not blob.startswith(b"ply\n") or end < 0:
@@ -85,15 +102,20 @@ def read_ply(path) -> Dict:
     counts = [ln for ln in lines if ln.startswith("element ")]
     if len(counts) != 1 or not counts[0].startswith("element vertex "):
         raise ValueError(f"{path}: one vertex element expected")
-    if tuple(ln for ln in lines if ln.startswith("property ")) != _PROPERTIES:
-        raise ValueError(f"{path}: vertex properties differ from x y z red green blue temperature")
+    properties = tuple(ln for ln in lines if ln.startswith("property "))
+    if properties not in (_PROPERTIES, _NORMAL_PROPERTIES):
+        raise ValueError(f"{path}: vertex properties differ from x y z [nx ny nz] red green blue temperature")
+    dtype = VERTEX_DTYPE if properties == _PROPERTIES else NORMAL_VERTEX_DTYPE
     m = int(counts[0].split()[2])
-    if len(blob) - body != m * VERTEX_DTYPE.itemsize:
-        raise ValueError(f"{path}: {len(blob) - body} body bytes for {m} vertices of {VERTEX_DTYPE.itemsize} bytes")
-    vertex = np.frombuffer(blob, dtype=VERTEX_DTYPE, count=m, offset=body)
-    return {"positions": np.stack([vertex["x"], vertex["y"], vertex["z"]], axis=1) if m else np.zeros((0, 3), np.float32),
-            "colors": np.stack([vertex["red"], vertex["green"], vertex["blue"]], axis=1) if m else np.zeros((0, 3), np.uint8),
-            "temperature": vertex["temperature"].copy(), "comments": comments}
+    if len(blob) - body != m * dtype.itemsize:
+        raise ValueError(f"{path}: {len(blob) - body} body bytes for {m} vertices of {dtype.itemsize} bytes")
+    vertex = np.frombuffer(blob, dtype=dtype, count=m, offset=body)
+    out = {"positions": np.stack([vertex["x"], vertex["y"], vertex["z"]], axis=1) if m else np.zeros((0, 3), np.float32),
+           "colors": np.stack([vertex["red"], vertex["green"], vertex["blue"]], axis=1) if m else np.zeros((0, 3), np.uint8),
+           "temperature": vertex["temperature"].copy(), "comments": comments}
+    if dtype is NORMAL_VERTEX_DTYPE:
+        out["normals"] = np.stack([vertex["nx"], vertex["ny"], vertex["nz"]], axis=1) if m else np.zeros((0, 3), np.float32)
+    return out
 
 
 # ---- triangle meshes ---------------------------------------------------------------------------------------------------------------

@@ -120,7 +120,8 @@ def pointcloud_append(origins: Tensor, directions: Tensor, depth: Tensor, accumu
 class ThermalPointCloud:
     """M points on the device: positions [M,3] float32, colors [M,3] uint8 (rendered RGB), temperature [M] float32 in degrees
     Celsius, thermal_colors [M,3] uint8 (the colour-mapped normalised temperature), source [M] int64 (camera * H * W + pixel of
-    the ray a point came from).  ``temperature_bounds``: the (min, max) degrees the normalised output was scaled with."""
+    the ray a point came from).  ``temperature_bounds``: the (min, max) degrees the normalised output was scaled with.  normals
+    [M,3] float32 (unit, or zero where none could be estimated) once ``estimate_normals`` has run."""
 
     positions: Tensor
     colors: Tensor
@@ -128,6 +129,7 @@ class ThermalPointCloud:
     thermal_colors: Optional[Tensor] = None
     source: Optional[Tensor] = None
     temperature_bounds: Optional[Tuple[float, float]] = None
+    normals: Optional[Tensor] = None
 
     def __len__(self) -> int:
         return int(self.positions.shape[0])
@@ -138,7 +140,7 @@ class ThermalPointCloud:
             return None if t is None else t[index]
 
         return ThermalPointCloud(pick(self.positions), pick(self.colors), pick(self.temperature), pick(self.thermal_colors),
-                                 pick(self.source), self.temperature_bounds)
+                                 pick(self.source), self.temperature_bounds, pick(self.normals))
 
 
 def subsample_indices(num_points: int, keep: int, device="cpu") -> Tensor:
@@ -209,6 +211,8 @@ class PointCloudExporter:
         self.params = pointcloud_params(min_accumulation, box[0], box[1], lo, hi, max_temperature, min_temperature, to_world)
         self._engine = None
         self.last_rays = 0  # rays cast by the last export
+        self.camera_viewpoints = None  # float32 [cameras.size, 3] on the device: where the last export's cameras stood (NaN rows: not rendered)
+        self._rays_per_camera = 0
 
     def _render(self, origins: Tensor, directions: Tensor, out):
         from ..engine import RayRenderEngine
@@ -255,18 +259,32 @@ class PointCloudExporter:
             count = torch.zeros((1,), dtype=torch.int64, device=dev)
             workspace = torch.empty((max(workspace_bytes(n), 8),), dtype=torch.uint8, device=dev)
             table = colormaps.get_table(self.thermal_color_map, dev)[1]
+            viewpoints = torch.full((cameras.size, 3), float("nan"), dtype=torch.float32, device=dev)
+            to_world = torch.tensor(list(self.params.to_world), dtype=torch.float32, device=dev).reshape(3, 4)
             out = None
             for k in index:
                 rb = cameras.generate_rays(k, device=dev, flat=True)
                 if adjust:
                     opt.apply_to_raybundle(rb)  # camera_indices = k for every ray of the pose
+                viewpoints[k] = to_world[:, :3] @ rb.origins[0] + to_world[:, 3]  # the corrected pose's centre, as the points are mapped
                 out = self._render(rb.origins, rb.directions, out)
                 pointcloud_append(rb.origins, rb.directions, out[self.depth_output_name], out["accumulation"], out["rgb"],
                                   out["thermal"], self.params, positions=positions, colors=colors, temperature=temperature,
                                   count=count, thermal_colors=thermal_colors, thermal_table=table, source=source,
                                   source_base=k * n, capacity=capacity, workspace=workspace)
             kept = int(count.item())  # the one synchronising read
+        self.camera_viewpoints, self._rays_per_camera = viewpoints, n
         if kept > capacity:
             raise RuntimeError(f"the point cloud holds {kept} points but max_points = {capacity}; raise max_points or tighten the filter")
         return ThermalPointCloud(positions[:kept], colors[:kept], temperature[:kept], thermal_colors[:kept], source[:kept],
                                  self.temperature_bounds)
+
+    def viewpoints(self, cloud: ThermalPointCloud) -> Tensor:
+        """float32 [M,3]: for every point of ``cloud`` (a cloud of the last ``export``, or a selection of it) the centre of the camera
+        it was seen from — the ray origin after the optimizer's correction, mapped through ``to_world`` like the points — gathered
+        through ``cloud.source // (H * W)``.  What ``estimate_normals`` turns the normals towards."""
+        if self.camera_viewpoints is None:
+            raise RuntimeError("viewpoints() follows export()")
+        if cloud.source is None:
+            raise ValueError("the cloud carries no source indices")
+        return self.camera_viewpoints[cloud.source // self._rays_per_camera]

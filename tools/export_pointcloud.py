@@ -13,6 +13,11 @@ Every camera of the chosen split of DATASET is rendered; a ray becomes a point w
 Positions are written in the dataset's original world frame (the inverse of the dataparser's orientation, centring and
 scaling); ``--scene-frame`` keeps the normalised frame the model was trained in.  ``--num-points`` thins a larger cloud evenly
 and deterministically (point floor(j M / N) for j < N).
+
+``--remove-outliers`` drops the floaters first (statistical outlier removal over ``--outlier-neighbors`` neighbours: a point goes
+when its mean neighbour distance is ``--outlier-std-ratio`` standard deviations above the cloud's mean); ``--normals`` gives every
+written point a normal (nx ny nz in the file) from its ``--normal-neighbors`` nearest neighbours, turned towards the camera the
+point was seen from.  Order: export, outlier removal, thinning, normals — the normals are those of the cloud that is written.
 """
 from __future__ import annotations
 
@@ -58,8 +63,19 @@ def parse(argv=None) -> argparse.Namespace:
     ap.add_argument("--colors", choices=("rgb", "thermal"), default="rgb", help="what fills red / green / blue")
     ap.add_argument("--scene-frame", action="store_true", help="write the normalised scene frame, not the dataset's world frame")
     ap.add_argument("--config-json", type=Path, default=None, help="model fields that override the run's config.json")
+    ap.add_argument("--remove-outliers", action="store_true", help="drop statistical outliers before thinning")
+    ap.add_argument("--outlier-neighbors", type=int, default=20, help="neighbours of the outlier statistic, the point included")
+    ap.add_argument("--outlier-std-ratio", type=float, default=10.0, help="standard deviations above the mean that make an outlier")
+    ap.add_argument("--normals", action="store_true", help="estimate a normal per written point (nx ny nz in the file)")
+    ap.add_argument("--normal-neighbors", type=int, default=30, help="nearest neighbours a normal is fitted to")
     ap.add_argument("--device", default="cuda")
     args = ap.parse_args(argv)
+    if not 2 <= args.outlier_neighbors <= 33:
+        ap.error("--outlier-neighbors must be 2 .. 33 (the point and up to 32 others)")
+    if not args.outlier_std_ratio > 0.0:
+        ap.error("--outlier-std-ratio must be positive")
+    if not 2 <= args.normal_neighbors <= 32:
+        ap.error("--normal-neighbors must be 2 .. 32")
     if (args.bounding_box_min is None) != (args.bounding_box_max is None):
         ap.error("--bounding-box-min and --bounding-box-max go together")
     if args.no_bounding_box and args.bounding_box_min is not None:
@@ -114,9 +130,19 @@ def main(argv=None) -> int:
     exporter, cameras, adjust = build_exporter(args)
     cloud = exporter.export(cameras, apply_camera_optimizer=adjust)
     kept = len(cloud)
+    removed = ""
+    if args.remove_outliers:
+        from thermo_nerf_amd.export import remove_statistical_outliers
+
+        cloud, _ = remove_statistical_outliers(cloud, args.outlier_neighbors, args.outlier_std_ratio)
+        removed = f", outliers removed {kept - len(cloud)}"
     cloud = subsample(cloud, args.num_points)
+    if args.normals:
+        from thermo_nerf_amd.export import estimate_normals
+
+        cloud = estimate_normals(cloud, args.normal_neighbors, exporter.viewpoints(cloud))
     write_ply(args.output, cloud, colors=args.colors)
-    print(f"rays cast {exporter.last_rays}, kept {kept}, written {len(cloud)} -> {args.output}")
+    print(f"rays cast {exporter.last_rays}, kept {kept}{removed}, written {len(cloud)} -> {args.output}")
     if len(cloud):
         print(f"temperature min {float(cloud.temperature.min()):.3f} C, max {float(cloud.temperature.max()):.3f} C")
     else:
