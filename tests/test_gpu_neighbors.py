@@ -71,8 +71,14 @@ def same(got, want, what=""):
     assert mean.tobytes() == want["mean_distance"].tobytes(), f"{what}: mean distance differs"
 
 
-@pytest.mark.parametrize("k", [1, 8, 19, 32])
-def test_knn_equals_the_reference_bit_for_bit(k):
+@pytest.mark.parametrize("k,resolution", [(1, 0), (8, 0), (19, 0), (32, 0), (8, 10), (8, 11), (8, 102)],
+                         ids=["1", "8", "19", "32", "8-grid10", "8-grid11", "8-grid102"])
+def test_knn_equals_the_reference_bit_for_bit(k, resolution):
+    """an explicit grid: 3000 points over 10^3 cells (one tile of 1024 cells), 11^3 (two tiles, the last one partial) and 102^3
+    (1037 tiles: a second pass of the 1024-wide scan) — the block-wide count, the tile scan and the cell offsets at their sizes"""
+    if resolution:
+        same(run_raw(cloud("random:3000"), k, resolution), reference("random:3000", k), f"random:3000 k={k} grid {resolution}")
+        return
     for n in sorted({1, 2, k, k + 1, 63, 64, 65, 257}):
         name = f"random:{n}"
         same(run_raw(cloud(name), k), reference(name, k), f"{name} k={k}")

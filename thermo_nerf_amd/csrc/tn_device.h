@@ -17,6 +17,33 @@ __device__ __forceinline__ float mul_rn(float a, float b) { return __fmul_rn(a, 
 __device__ __forceinline__ float add_rn(float a, float b) { return __fadd_rn(a, b); }
 __device__ __forceinline__ float sub_rn(float a, float b) { return __fsub_rn(a, b); }
 
+// one row m[0..3] of a 3 x 4 affine map applied to p, in this association only: ((m0 p0 + m1 p1) + m2 p2) + m3
+__device__ __forceinline__ float affine_row(const float *m, const float *p) {
+    return add_rn(add_rn(add_rn(mul_rn(m[0], p[0]), mul_rn(m[1], p[1])), mul_rn(m[2], p[2])), m[3]);
+}
+
+// float -> byte of the 8-bit outputs (frames, clouds, meshes): trunc, saturated; NaN -> 0 (fmaxf returns the other operand)
+__device__ __forceinline__ uint32_t quantise(float v) { return (uint32_t)(int)fminf(fmaxf(v, 0.0f), 255.0f); }
+
+// a uint8 [256][3] colour table -> one packed dword r | g << 8 | b << 16 per entry in LDS, by a block of THREADS threads.  No
+// barrier inside: the caller's next one orders the fill before the first lut_entry.
+template <int THREADS>
+__device__ __forceinline__ void load_lut(uint32_t *lut, const uint8_t *__restrict__ table) {
+    for (int e = threadIdx.x; e < 256; e += THREADS)
+        lut[e] = (uint32_t)table[3 * e] | (uint32_t)table[3 * e + 1] << 8 | (uint32_t)table[3 * e + 2] << 16;
+}
+
+// the TN_FRAME_LUT lookup of x (tn_frame.hip): entry trunc(x * 256), x < 0 -> entry 0, 256 and above -> entry 255.  x is not a
+// NaN here (it would read entry 0); lut_entry_nan maps a NaN to (0, 0, 0) first.
+__device__ __forceinline__ uint32_t lut_entry(const uint32_t *lut, float x) { return lut[(int)quantise(mul_rn(x, 256.0f))]; }
+__device__ __forceinline__ uint32_t lut_entry_nan(const uint32_t *lut, float x) { return x != x ? 0u : lut_entry(lut, x); }
+
+__device__ __forceinline__ void store_rgb8(uint8_t *dst, uint32_t packed) {
+    dst[0] = (uint8_t)packed;
+    dst[1] = (uint8_t)(packed >> 8);
+    dst[2] = (uint8_t)(packed >> 16);
+}
+
 // torch.nan_to_num defaults: nan -> 0, +inf -> FLT_MAX, -inf -> -FLT_MAX
 __device__ __forceinline__ float nan_to_num(float x) {
     if (x != x) return 0.0f;
@@ -643,6 +670,11 @@ static inline bool tn_ensure_dynamic_lds(size_t bytes) {
     return true;
 }
 #endif
+
+namespace tn {  // host side: the entry points' argument checks and grid sizes (a null pointer is aligned)
+inline bool misaligned(const void *p, uintptr_t a) { return reinterpret_cast<uintptr_t>(p) % a != 0; }
+inline long long ceil_div(long long n, long long d) { return (n + d - 1) / d; }
+}  // namespace tn
 
 #define TN_LAUNCH_CHECK()                                  \
     do {                                                   \

@@ -22,10 +22,6 @@ namespace {
 constexpr int kBlock = 256;
 constexpr int kMaxBlocks = 2048;  // grid-stride beyond
 
-__device__ __forceinline__ uint32_t quantise(float v) {  // trunc, saturated; NaN -> 0 (fmaxf returns the other operand)
-    return (uint32_t)(int)fminf(fmaxf(v, 0.0f), 255.0f);
-}
-
 struct DepthArgs {
     float near, denom;
 };
@@ -37,12 +33,7 @@ __device__ __forceinline__ uint32_t finish_pixel(const float *x, float a, const 
         if (C == 1) return quantise(mul_rn(x[0], 255.0f)) * 0x010101u;
         return quantise(mul_rn(x[0], 255.0f)) | quantise(mul_rn(x[1], 255.0f)) << 8 | quantise(mul_rn(x[2], 255.0f)) << 16;
     }
-    if (MODE == TN_FRAME_LUT) {  // (the reference looks channel 0 up: cmap(image[:, :, 0]))
-        const float v = x[0];
-        if (v != v) return 0u;
-        const float t = mul_rn(v, 256.0f);  // exact
-        return lut[(int)fminf(fmaxf(t, 0.0f), 255.0f)];  // (t == 256 and everything above: entry 255)
-    }
+    if (MODE == TN_FRAME_LUT) return lut_entry_nan(lut, x[0]);  // (the reference looks channel 0 up: cmap(image[:, :, 0]))
     float t = __fdiv_rn(sub_rn(x[0], da.near), da.denom);
     t = fminf(fmaxf(t, 0.0f), 1.0f);  // clip; NaN -> 0
     const int i = (int)mul_rn(t, 255.0f);
@@ -61,8 +52,7 @@ frame_to_rgb8_kernel(const float *__restrict__ src, const float *__restrict__ ac
     __shared__ float lutf[MODE == TN_FRAME_DEPTH ? 768 : 1];
     DepthArgs da{0.0f, 1.0f};
     if (MODE == TN_FRAME_LUT) {
-        const uint8_t *t = reinterpret_cast<const uint8_t *>(table);
-        for (int e = threadIdx.x; e < 256; e += kBlock) lut[e] = (uint32_t)t[3 * e] | (uint32_t)t[3 * e + 1] << 8 | (uint32_t)t[3 * e + 2] << 16;
+        load_lut<kBlock>(lut, reinterpret_cast<const uint8_t *>(table));
         __syncthreads();
     }
     if (MODE == TN_FRAME_DEPTH) {
@@ -111,10 +101,7 @@ frame_to_rgb8_kernel(const float *__restrict__ src, const float *__restrict__ ac
         float x[C];
 #pragma unroll
         for (int q = 0; q < C; ++q) x[q] = src[p * C + q];
-        const uint32_t c = finish_pixel<MODE, C>(x, MODE == TN_FRAME_DEPTH ? acc[p] : 0.0f, lut, lutf, da);
-        dst[3 * p] = (uint8_t)c;
-        dst[3 * p + 1] = (uint8_t)(c >> 8);
-        dst[3 * p + 2] = (uint8_t)(c >> 16);
+        store_rgb8(dst + 3 * p, finish_pixel<MODE, C>(x, MODE == TN_FRAME_DEPTH ? acc[p] : 0.0f, lut, lutf, da));
     }
 }
 

@@ -9,9 +9,9 @@
 //   3. (memset) the cell counters <- 0
 //   4. bin      a point's cell (stored per point) and an integer atomicAdd on its counter; a non-finite point writes its own
 //               all -1 / +inf row here and takes no further part
-//   5. tiles    one block per tile of kCellTile cells: the tile's number of points
-//   6. scan     ONE block (tn_scan.h): tile -> the number of points before it; the total = the number of finite points
-//   7. offsets  one block per tile: every cell <- the position of its first point
+//   5. tiles    one block per tile of kCellTile cells: the tile's number of points (block_exclusive's total, tn_scan.h)
+//   6. scan     ONE block (scan_tiles): tile -> the number of points before it; the total = the number of finite points
+//   7. offsets  one block per tile: every cell <- the position of its first point (block_exclusive again)
 //   8. scatter  a point takes the next position of its cell (atomicAdd) and stores (x, y, z, index) there; afterwards a
 //               cell's counter is the END of its range and the START of the next cell's
 //   9. search   one thread per query, queries in cell order (a wave reads neighbouring cells): shells of cells of Chebyshev
@@ -82,7 +82,7 @@ inline int choose_resolution(long long n) {  // grid_resolution == 0: about one 
 inline Layout layout_of(long long n, int res) {
     Layout l;
     l.num_cells = (long long)res * res * res;
-    l.num_tiles = (l.num_cells + kCellTile - 1) / kCellTile;
+    l.num_tiles = ceil_div(l.num_cells, kCellTile);
     size_t o = 0;
     l.sorted = o;     o += align16((size_t)n * sizeof(float4));
     l.info = o;       o += align16(sizeof(GridInfo));
@@ -206,19 +206,10 @@ bin_kernel(const float *__restrict__ positions, long long n, int k, const GridIn
 // ---- 5. 6. 7. cell counts -> cell starts --------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(kBlock)
 tiles_kernel(const uint32_t *__restrict__ cells, long long *__restrict__ tiles) {
-    __shared__ uint32_t wave_sum_[kWaves];
     const uint4 v = reinterpret_cast<const uint4 *>(cells)[(size_t)blockIdx.x * kBlock + threadIdx.x];
-    uint32_t s = v.x + v.y + v.z + v.w;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, TN_WAVE);
-    if (threadIdx.x % TN_WAVE == 0) wave_sum_[threadIdx.x / TN_WAVE] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t sum = 0;
-#pragma unroll
-        for (int w = 0; w < kWaves; ++w) sum += wave_sum_[w];
-        tiles[blockIdx.x] = (long long)sum;
-    }
+    uint32_t total;
+    block_exclusive<kBlock>(v.x + v.y + v.z + v.w, total);
+    if (threadIdx.x == 0) tiles[blockIdx.x] = (long long)total;
 }
 
 __global__ void __launch_bounds__(kScan)
@@ -228,24 +219,11 @@ scan_kernel(long long *__restrict__ tiles, long long num_tiles, long long *__res
 
 __global__ void __launch_bounds__(kBlock)
 offsets_kernel(uint32_t *__restrict__ cells, const long long *__restrict__ tiles) {
-    __shared__ uint32_t wave_total[kWaves];
-    const int lane = threadIdx.x % TN_WAVE, wave = threadIdx.x / TN_WAVE;
     uint4 *slot = reinterpret_cast<uint4 *>(cells) + (size_t)blockIdx.x * kBlock + threadIdx.x;
     const uint4 v = *slot;
-    const uint32_t own = v.x + v.y + v.z + v.w;
-    uint32_t incl = own;
-#pragma unroll
-    for (int o = 1; o < TN_WAVE; o <<= 1) {
-        const uint32_t up = __shfl_up(incl, o, TN_WAVE);
-        if (lane >= o) incl += up;
-    }
-    if (lane == TN_WAVE - 1) wave_total[wave] = incl;
-    __syncthreads();
-    uint32_t before = (uint32_t)tiles[blockIdx.x];
-#pragma unroll
-    for (int w = 0; w < kWaves; ++w) before += w < wave ? wave_total[w] : 0u;
+    uint32_t total;
     uint4 start;
-    start.x = before + incl - own;
+    start.x = (uint32_t)tiles[blockIdx.x] + block_exclusive<kBlock>(v.x + v.y + v.z + v.w, total);
     start.y = start.x + v.x;
     start.z = start.y + v.y;
     start.w = start.z + v.z;
@@ -472,8 +450,6 @@ normals_kernel(const float *__restrict__ positions, const int32_t *__restrict__ 
     for (int c = 0; c < 3; ++c) normals[3 * i + c] = (float)(flip ? -nv[c] : nv[c]);
 }
 
-inline bool misaligned(const void *p, uintptr_t a) { return reinterpret_cast<uintptr_t>(p) % a != 0; }
-
 inline bool bad_resolution(int32_t r) { return r < 0 || r > kMaxRes; }
 
 }  // namespace
@@ -509,7 +485,7 @@ int tn_knn(const float *positions, int64_t num_points, int32_t k, int32_t grid_r
     long long *tiles = reinterpret_cast<long long *>(ws + l.tiles);
     uint32_t *cells = reinterpret_cast<uint32_t *>(ws + l.cells);
     int32_t *point_cell = reinterpret_cast<int32_t *>(ws + l.point_cell);
-    const long long point_blocks = (n + kBlock - 1) / kBlock;
+    const long long point_blocks = ceil_div(n, kBlock);
     const int box_blocks = (int)(point_blocks < kBoxBlocks ? point_blocks : kBoxBlocks);
     hipLaunchKernelGGL(box_kernel, dim3(box_blocks), dim3(kBlock), 0, s, positions, n, partials);
     TN_LAUNCH_CHECK();
@@ -527,7 +503,7 @@ int tn_knn(const float *positions, int64_t num_points, int32_t k, int32_t grid_r
     TN_LAUNCH_CHECK();
     hipLaunchKernelGGL(scatter_kernel, dim3((unsigned)point_blocks), dim3(kBlock), 0, s, positions, n, point_cell, cells, sorted);
     TN_LAUNCH_CHECK();
-    const long long search_blocks = (n + kSearch - 1) / kSearch;
+    const long long search_blocks = ceil_div(n, kSearch);
     hipLaunchKernelGGL(search_kernel, dim3((unsigned)search_blocks), dim3(kSearch), (size_t)k * kSearch * 8, s, sorted, count, (int)k, info,
                        cells, neighbor_index, neighbor_d2, mean_distance);
     TN_LAUNCH_CHECK();
@@ -543,7 +519,7 @@ int tn_pointcloud_normals(const float *positions, const int32_t *neighbor_index,
     if (num_points == 0) return TN_OK;
     if (!positions || !neighbor_index || !normals) return TN_ERR_NULL;
     const long long n = num_points;
-    hipLaunchKernelGGL(normals_kernel, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, (hipStream_t)stream, positions,
+    hipLaunchKernelGGL(normals_kernel, dim3((unsigned)ceil_div(n, kBlock)), dim3(kBlock), 0, (hipStream_t)stream, positions,
                        neighbor_index, n, (int)k, viewpoints, normals);
     TN_LAUNCH_CHECK();
     return TN_OK;

@@ -6,21 +6,22 @@
 //
 // tn_tsdf_integrate: one plain launch per pose, one thread per voxel, x fastest: the seven planes are coalesced streams, a voxel
 // is read, updated and written by its own thread only (no atomics), a skipped voxel writes nothing.
-// tn_mesh_extract: six plain launches, the ordered count / scan / emit of tn_pointcloud.hip twice:
-//   1. count   active cells per tile of kTile cells (64-bit ballot + popcount per wave)        -> cell_tiles[b]
+// tn_mesh_extract: six plain launches, the ordered count / scan / emit of tn_pointcloud.hip twice, on the block-wide primitives
+// of tn_scan.h:
+//   1. count   active cells per tile of kTile cells (block_rank's total)                        -> cell_tiles[b]
 //   2. scan    ONE block: exclusive prefix of the tile counts, counts[0] <- the number of vertices
-//   3. emit    the predicate again, rank from the ballot mask: cell_index[cell] <- vertex index or -1 for EVERY cell, vertex
-//              data only below capacity_vertices
+//   3. emit    the predicate again, block_rank: cell_index[cell] <- vertex index or -1 for EVERY cell, vertex data only below
+//              capacity_vertices
 //   4. count   triangles per tile of kTile grid points (0, 2, 4 or 6 per point: a quad per crossing edge p -> p + e_a whose four
-//              cells are active)                                                                -> point_tiles[b]
+//              cells are active; block_exclusive's total)                                       -> point_tiles[b]
 //   5. scan    counts[1] <- the number of triangles
-//   6. emit    the predicate again, in-wave exclusive prefix by a shuffle scan of the per-lane counts; nothing at or beyond
-//              capacity_triangles
+//   6. emit    the predicate again, block_exclusive of the per-point counts; nothing at or beyond capacity_triangles
 // No atomics, no allocation, no host synchronisation, and NO block ever waits for another block (no look-back, no grid barrier,
 // no cooperative launch).  One block per tile, uncapped.
 //
-// Traffic (an estimate from the bytes, not a measurement: tools/mesh_bench.py): a pose reads and writes at most 7 planes = 56 B
-// per voxel; the extraction reads 2 planes 8 times per cell, twice, which the caches mostly absorb.
+// Traffic: a pose reads and writes at most 7 planes = 56 B per voxel; the extraction reads 2 planes 8 times per cell, twice, which
+// the caches mostly absorb.  Measured at 256^3 (tools/mesh_bench.py, profiles/micro/export_mesh.txt): 0.23 ms per 1080p pose beside
+// 30.9 ms of rendering, 1.07 ms for the extraction.
 #include "tn_device.h"
 #include "tn_scan.h"
 
@@ -29,15 +30,10 @@ using namespace tn;
 namespace {
 
 constexpr int kTile = 256;  // cells / grid points per tile = threads per block of every kernel but the scan
-constexpr int kWaves = kTile / TN_WAVE;
 
 // correctly rounded fp32 quotient and root through fp64 (see the head of the file)
 __device__ __forceinline__ float div_rn(float a, float b) { return (float)((double)a / (double)b); }
 __device__ __forceinline__ float sqrt_rn(float a) { return (float)sqrt((double)a); }
-
-__device__ __forceinline__ uint32_t quantise(float v) {  // trunc, saturated; NaN -> 0 (fmaxf returns the other operand)
-    return (uint32_t)(int)fminf(fmaxf(v, 0.0f), 255.0f);
-}
 
 struct Dims {
     int nx, ny, nz;
@@ -66,12 +62,7 @@ integrate_kernel(const float *__restrict__ depth, const float *__restrict__ accu
     if (vox >= d.points) return;
     const int i = (int)(vox % d.nx), j = (int)(vox / d.nx % d.ny), k = (int)(vox / ((long long)d.nx * d.ny));
     const float p[3] = {grid_coord(q, 0, (float)i), grid_coord(q, 1, (float)j), grid_coord(q, 2, (float)k)};
-    float c[3];
-#pragma unroll
-    for (int r = 0; r < 3; ++r) {
-        const float *m = q.w2c + 4 * r;
-        c[r] = add_rn(add_rn(add_rn(mul_rn(m[0], p[0]), mul_rn(m[1], p[1])), mul_rn(m[2], p[2])), m[3]);
-    }
+    const float c[3] = {affine_row(q.w2c, p), affine_row(q.w2c + 4, p), affine_row(q.w2c + 8, p)};
     const float zc = -c[2];  // the camera looks along -z
     if (!(zc > 0.0f)) return;
     const float u = add_rn(div_rn(mul_rn(q.fx, c[0]), zc), q.cx);
@@ -125,25 +116,13 @@ __device__ __forceinline__ bool cell_active(const float *__restrict__ volume, co
     return all && inside > 0 && inside < 8;
 }
 
-// the block's count of `keep` -> tiles[blockIdx.x]
-__device__ __forceinline__ void tile_count(bool keep, long long *__restrict__ tiles) {
-    __shared__ uint32_t wave_count[kWaves];
-    const unsigned long long mask = __ballot(keep);
-    if (threadIdx.x % TN_WAVE == 0) wave_count[threadIdx.x / TN_WAVE] = (uint32_t)__popcll(mask);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t sum = 0;
-#pragma unroll
-        for (int w = 0; w < kWaves; ++w) sum += wave_count[w];
-        tiles[blockIdx.x] = (long long)sum;
-    }
-}
-
 __global__ void __launch_bounds__(kTile)
 count_cells_kernel(const float *__restrict__ volume, Dims d, long long *__restrict__ tiles) {
     const long long cell = (long long)blockIdx.x * kTile + threadIdx.x;
     Cell c;
-    tile_count(cell < d.cells && cell_active(volume, d, cell, c), tiles);
+    uint32_t total;
+    block_rank<kTile>(cell < d.cells && cell_active(volume, d, cell, c), total);
+    if (threadIdx.x == 0) tiles[blockIdx.x] = (long long)total;
 }
 
 template <bool APPEND>
@@ -157,26 +136,18 @@ emit_vertices_kernel(const float *__restrict__ volume, tn_mesh_params q, Dims d,
                      const long long *__restrict__ tiles, int *__restrict__ cell_index, float *__restrict__ positions,
                      uint8_t *__restrict__ colors, float *__restrict__ temperature, uint8_t *__restrict__ thermal_colors,
                      long long capacity) {
-    __shared__ uint32_t wave_count[kWaves];
     __shared__ uint32_t lut[256];
-    if (thermal_colors)
-        for (int e = threadIdx.x; e < 256; e += kTile)
-            lut[e] = (uint32_t)table[3 * e] | (uint32_t)table[3 * e + 1] << 8 | (uint32_t)table[3 * e + 2] << 16;
+    if (thermal_colors) load_lut<kTile>(lut, table);
     const long long cell = (long long)blockIdx.x * kTile + threadIdx.x;
     Cell c;
     const bool keep = cell < d.cells && cell_active(volume, d, cell, c);
-    const unsigned long long mask = __ballot(keep);
-    const int wave = threadIdx.x / TN_WAVE;
-    if (threadIdx.x % TN_WAVE == 0) wave_count[wave] = (uint32_t)__popcll(mask);
-    __syncthreads();
+    uint32_t total;
+    const uint32_t rank = block_rank<kTile>(keep, total);  // its barrier is also the one between the table's fill and its reads
     if (cell >= d.cells) return;
     if (!keep) {
         cell_index[cell] = -1;
         return;
     }
-    uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
-#pragma unroll
-    for (int w = 0; w < kWaves; ++w) rank += w < wave ? wave_count[w] : 0u;
     const long long dst = tiles[blockIdx.x] + (long long)rank;  // < the number of cells <= 2^31 - 1
     cell_index[cell] = (int)dst;
     if (dst >= capacity) return;
@@ -214,17 +185,11 @@ emit_vertices_kernel(const float *__restrict__ volume, tn_mesh_params q, Dims d,
     const float mean_thermal = div_rn(sum[0], sum[4]);
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
-        const float *m = q.to_world + 4 * a;
-        positions[3 * dst + a] = add_rn(add_rn(add_rn(mul_rn(m[0], p[0]), mul_rn(m[1], p[1])), mul_rn(m[2], p[2])), m[3]);
+        positions[3 * dst + a] = affine_row(q.to_world + 4 * a, p);
         colors[3 * dst + a] = (uint8_t)quantise(mul_rn(div_rn(sum[1 + a], sum[4]), 255.0f));
     }
     temperature[dst] = add_rn(mul_rn(mean_thermal, q.temperature_span), q.temperature_min);
-    if (thermal_colors) {  // TN_FRAME_LUT of tn_frame.hip; NaN -> (0, 0, 0)
-        const uint32_t e = mean_thermal != mean_thermal ? 0u : lut[(int)fminf(fmaxf(mul_rn(mean_thermal, 256.0f), 0.0f), 255.0f)];
-        thermal_colors[3 * dst] = (uint8_t)e;
-        thermal_colors[3 * dst + 1] = (uint8_t)(e >> 8);
-        thermal_colors[3 * dst + 2] = (uint8_t)(e >> 16);
-    }
+    if (thermal_colors) store_rgb8(thermal_colors + 3 * dst, lut_entry_nan(lut, mean_thermal));  // NaN -> (0, 0, 0)
 }
 
 struct Quads {
@@ -264,42 +229,22 @@ __device__ __forceinline__ int point_quads(const float *__restrict__ volume, con
 
 __global__ void __launch_bounds__(kTile)
 count_triangles_kernel(const float *__restrict__ volume, Dims d, const int *__restrict__ cell_index, long long *__restrict__ tiles) {
-    __shared__ uint32_t wave_count[kWaves];
     const long long g = (long long)blockIdx.x * kTile + threadIdx.x;
     Quads qd;
-    uint32_t own = g < d.points ? 2u * (uint32_t)point_quads(volume, d, cell_index, g, qd) : 0u;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) own += __shfl_xor(own, o, TN_WAVE);
-    if (threadIdx.x % TN_WAVE == 0) wave_count[threadIdx.x / TN_WAVE] = own;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t sum = 0;
-#pragma unroll
-        for (int w = 0; w < kWaves; ++w) sum += wave_count[w];
-        tiles[blockIdx.x] = (long long)sum;
-    }
+    uint32_t total;
+    block_exclusive<kTile>(g < d.points ? 2u * (uint32_t)point_quads(volume, d, cell_index, g, qd) : 0u, total);
+    if (threadIdx.x == 0) tiles[blockIdx.x] = (long long)total;
 }
 
 __global__ void __launch_bounds__(kTile)
 emit_triangles_kernel(const float *__restrict__ volume, Dims d, const int *__restrict__ cell_index,
                       const long long *__restrict__ tiles, int *__restrict__ triangles, long long capacity) {
-    __shared__ uint32_t wave_count[kWaves];
     const long long g = (long long)blockIdx.x * kTile + threadIdx.x;
-    const int lane = threadIdx.x % TN_WAVE, wave = threadIdx.x / TN_WAVE;
     Quads qd;
     const uint32_t own = g < d.points ? 2u * (uint32_t)point_quads(volume, d, cell_index, g, qd) : 0u;
-    uint32_t incl = own;  // the in-wave inclusive prefix of the per-lane counts
-#pragma unroll
-    for (int o = 1; o < TN_WAVE; o <<= 1) {
-        const uint32_t up = __shfl_up(incl, o, TN_WAVE);
-        if (lane >= o) incl += up;
-    }
-    if (lane == TN_WAVE - 1) wave_count[wave] = incl;
-    __syncthreads();
+    uint32_t total;
+    const uint32_t before = block_exclusive<kTile>(own, total);
     if (own == 0u) return;
-    uint32_t before = incl - own;
-#pragma unroll
-    for (int w = 0; w < kWaves; ++w) before += w < wave ? wave_count[w] : 0u;
     long long dst = tiles[blockIdx.x] + (long long)before;
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
@@ -319,9 +264,7 @@ emit_triangles_kernel(const float *__restrict__ volume, Dims d, const int *__res
     }
 }
 
-inline bool misaligned(const void *p, uintptr_t a) { return reinterpret_cast<uintptr_t>(p) % a != 0; }
-
-inline long long tiles_of(long long items) { return (items + kTile - 1) / kTile; }
+inline long long tiles_of(long long items) { return ceil_div(items, kTile); }
 
 inline size_t index_bytes(long long cells) { return ((size_t)cells * sizeof(int) + 7) / 8 * 8; }
 

@@ -4,20 +4,19 @@
 // correctly rounded fp32 operation (explicit *_rn intrinsics), so a cloud is defined bit for bit (include/thermonerf_hip.h).
 //
 // Three plain launches per call, no host synchronisation, no allocation:
-//   1. count   one block per tile of kTile rays: the predicate, a 64-bit ballot + popcount per wave, the block's sum -> tile[b]
+//   1. count   one block per tile of kTile rays: the predicate, the block's number of kept rays (block_rank, tn_scan.h) -> tile[b]
 //   2. scan    ONE block: count_in = count[0]; tile[b] <- count_in + (exclusive prefix of the tile counts), kScan tiles per
 //              pass with a running carry; count[0] <- count_in + kept (the full number, also beyond the capacity)
-//   3. emit    the predicate again (the same device function on the same inputs: the same bits), in-wave rank from the ballot
-//              mask (mbcnt), wave bases from LDS, destination = tile[b] + wave base + rank; nothing is written at an index
-//              >= capacity
+//   3. emit    the predicate again (the same device function on the same inputs: the same bits), the ray's rank among the
+//              block's kept rays (block_rank again), destination = tile[b] + rank; nothing is written at an index >= capacity
 // The order of the output is a prefix sum, never the arrival order of atomics, and NO block ever waits for another block: no
 // decoupled look-back, no grid barrier, no cooperative launch — a block that spins on a tile which is not resident is how a
 // shared card gets hung.  One block per tile, uncapped (no grid-stride, hence no cap boundary).
 //
 // A lane owns one ray; every access is a 4-byte (8-byte for the int64 arrays) element access, so inputs may start at any ray of
-// a larger allocation.  Traffic: 36 B per ray in the count pass, 48 B per ray in the emit pass, <= 30 B per survivor — by
-// that count a few tens of microseconds per 1080p pose beside a ~30 ms render (an estimate from the bytes, not a measurement:
-// tools/export_bench.py).  Like tn_frame.hip the kernels are launch- and latency-bound and not a tuning target.
+// a larger allocation.  Traffic: 36 B per ray in the count pass, 48 B per ray in the emit pass, <= 30 B per survivor; measured
+// 0.07 ms per 1080p pose with half of the rays kept, beside a 31 ms render (tools/export_bench.py,
+// profiles/micro/export_pointcloud.txt).  Like tn_frame.hip the kernels are launch- and latency-bound and not a tuning target.
 #include "tn_device.h"
 #include "tn_scan.h"
 
@@ -26,7 +25,6 @@ using namespace tn;
 namespace {
 
 constexpr int kTile = 256;    // rays per tile = threads per block of the count and emit kernels
-constexpr int kWaves = kTile / TN_WAVE;
 
 struct Ray {  // what the predicate leaves behind for the emit
     float p[3];
@@ -48,27 +46,15 @@ __device__ __forceinline__ bool keep_ray(const float *__restrict__ origins, cons
     return keep && r.thermal > q.thermal_lo && r.thermal < q.thermal_hi;
 }
 
-__device__ __forceinline__ uint32_t quantise(float v) {  // trunc, saturated; NaN -> 0 (fmaxf returns the other operand)
-    return (uint32_t)(int)fminf(fmaxf(v, 0.0f), 255.0f);
-}
-
 __global__ void __launch_bounds__(kTile)
 count_kernel(const float *__restrict__ origins, const float *__restrict__ directions, const float *__restrict__ depth,
              const float *__restrict__ accumulation, const float *__restrict__ thermal, tn_pointcloud_params q, long long n,
              long long *__restrict__ tiles) {
-    __shared__ uint32_t wave_count[kWaves];
     const long long i = (long long)blockIdx.x * kTile + threadIdx.x;
     Ray r;
-    const bool keep = i < n && keep_ray(origins, directions, depth, accumulation, thermal, q, i, r);
-    const unsigned long long mask = __ballot(keep);
-    if (threadIdx.x % TN_WAVE == 0) wave_count[threadIdx.x / TN_WAVE] = (uint32_t)__popcll(mask);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t sum = 0;
-#pragma unroll
-        for (int w = 0; w < kWaves; ++w) sum += wave_count[w];
-        tiles[blockIdx.x] = (long long)sum;
-    }
+    uint32_t total;
+    block_rank<kTile>(i < n && keep_ray(origins, directions, depth, accumulation, thermal, q, i, r), total);
+    if (threadIdx.x == 0) tiles[blockIdx.x] = (long long)total;
 }
 
 __global__ void __launch_bounds__(kScan)
@@ -83,43 +69,28 @@ emit_kernel(const float *__restrict__ origins, const float *__restrict__ directi
             const long long *__restrict__ tiles, float *__restrict__ positions, uint8_t *__restrict__ colors,
             float *__restrict__ temperature, uint8_t *__restrict__ thermal_colors, long long *__restrict__ source,
             long long capacity) {
-    __shared__ uint32_t wave_count[kWaves];
     __shared__ uint32_t lut[256];
-    if (thermal_colors)
-        for (int e = threadIdx.x; e < 256; e += kTile)
-            lut[e] = (uint32_t)table[3 * e] | (uint32_t)table[3 * e + 1] << 8 | (uint32_t)table[3 * e + 2] << 16;
+    if (thermal_colors) load_lut<kTile>(lut, table);
     const long long i = (long long)blockIdx.x * kTile + threadIdx.x;
     Ray r;
     const bool keep = i < n && keep_ray(origins, directions, depth, accumulation, thermal, q, i, r);
-    const unsigned long long mask = __ballot(keep);
-    const int wave = threadIdx.x / TN_WAVE;
-    if (threadIdx.x % TN_WAVE == 0) wave_count[wave] = (uint32_t)__popcll(mask);
-    __syncthreads();
+    uint32_t total;
+    const uint32_t rank = block_rank<kTile>(keep, total);  // its barrier is also the one between the table's fill and its reads
     if (!keep) return;
-    uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
-#pragma unroll
-    for (int w = 0; w < kWaves; ++w) rank += w < wave ? wave_count[w] : 0u;
     const long long dst = tiles[blockIdx.x] + (long long)rank;
     if (dst >= capacity) return;
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
-        const float *m = q.to_world + 4 * c;
-        positions[3 * dst + c] = add_rn(add_rn(add_rn(mul_rn(m[0], r.p[0]), mul_rn(m[1], r.p[1])), mul_rn(m[2], r.p[2])), m[3]);
+        positions[3 * dst + c] = affine_row(q.to_world + 4 * c, r.p);
         colors[3 * dst + c] = (uint8_t)quantise(mul_rn(rgb[3 * i + c], 255.0f));
     }
     temperature[dst] = add_rn(mul_rn(r.thermal, q.temperature_span), q.temperature_min);
-    if (thermal_colors) {  // TN_FRAME_LUT of tn_frame.hip (a kept thermal is never NaN: it passed two comparisons)
-        const uint32_t e = lut[(int)fminf(fmaxf(mul_rn(r.thermal, 256.0f), 0.0f), 255.0f)];
-        thermal_colors[3 * dst] = (uint8_t)e;
-        thermal_colors[3 * dst + 1] = (uint8_t)(e >> 8);
-        thermal_colors[3 * dst + 2] = (uint8_t)(e >> 16);
-    }
+    // (a kept thermal is never NaN: it passed two comparisons)
+    if (thermal_colors) store_rgb8(thermal_colors + 3 * dst, lut_entry(lut, r.thermal));
     if (source) source[dst] = source_base + i;
 }
 
-inline bool misaligned(const void *p, uintptr_t a) { return reinterpret_cast<uintptr_t>(p) % a != 0; }
-
-inline long long tiles_of(long long num_rays) { return (num_rays + kTile - 1) / kTile; }
+inline long long tiles_of(long long num_rays) { return ceil_div(num_rays, kTile); }
 
 }  // namespace
 

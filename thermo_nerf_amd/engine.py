@@ -342,3 +342,15 @@ class RayRenderEngine:
         main = [b.elapsed_time(c) for _, b, c in self.timings]
         self.timings = []
         return prop, main
+
+
+def engine_for(model, cached: Optional[RayRenderEngine]) -> RayRenderEngine:
+    """THE engine-cache rule of everything that renders ``model`` pose after pose: ``cached`` (the caller's engine of the last call,
+    or None) is kept while its chunk and early-termination threshold are still the model's config, else a fresh engine is
+    built; either way ``rc.pdf_anneal`` follows the sampler.  The caller stores the result where it keeps ``cached``."""
+    chunk = int(model.config.eval_num_rays_per_chunk)
+    eng = cached
+    if eng is None or eng.chunk != chunk or eng.rc.early_stop_transmittance != float(model.config.early_termination_eps):
+        eng = RayRenderEngine(model, chunk=chunk)
+    eng.rc.pdf_anneal = float(model.proposal_sampler._anneal)
+    return eng

@@ -8,7 +8,6 @@ define every value bit for bit).  Nothing synchronises between poses; the two co
 """
 from __future__ import annotations
 
-import dataclasses
 import math
 from dataclasses import dataclass
 from typing import Optional, Sequence, Tuple
@@ -18,7 +17,7 @@ import torch
 from torch import Tensor
 
 from .. import _hip, colormaps
-from .pointcloud import _IDENTITY, _SCENE_BOX, _out
+from ._common import SCENE_BOX, PoseExporter, affine12, check_color_table, out_tensor, resolve_box, workspace_of
 
 PLANES = 7  # tsdf_sum, weight, thermal_sum, r_sum, g_sum, b_sum, colour_weight
 _POSE_CLAMP = float(np.float32(1e-4))  # the pose kernel's lower bound of |w|^2
@@ -89,11 +88,7 @@ def mesh_params(lo: Sequence[float], hi: Sequence[float], dims: Sequence[int], t
     q.min_accumulation = float(min_accumulation)
     q.temperature_span = float(max_temperature) - float(min_temperature)
     q.temperature_min = float(min_temperature)
-    m = _IDENTITY if to_world is None else tuple(float(v) for v in np.asarray(to_world, dtype=np.float64).reshape(-1))
-    if len(m) != 12:
-        raise ValueError("to_world is a 3 x 4 matrix")
-    for k in range(12):
-        q.to_world[k] = m[k]
+    q.to_world[:] = affine12(to_world)
     set_camera(q, *(camera if camera is not None else (1.0, 1.0, 0.0, 0.0, np.eye(3, 4))))
     return q
 
@@ -138,30 +133,24 @@ def mesh_extract(volume: Tensor, params, *, counts: Tensor, positions: Optional[
     cap_t = int(triangles.shape[0] if triangles is not None else 0) if capacity_triangles is None else int(capacity_triangles)
     if cap_v < 0 or cap_t < 0:
         raise ValueError("a capacity must not be negative")
-    positions = _out(positions, "positions", torch.float32, cap_v, 3)
-    colors = _out(colors, "colors", torch.uint8, cap_v, 3)
-    temperature = _out(temperature, "temperature", torch.float32, cap_v, 1)
-    thermal_colors = _out(thermal_colors, "thermal_colors", torch.uint8, cap_v, 3)
-    triangles = _out(triangles, "triangles", torch.int32, cap_t, 3)
-    counts = _out(counts, "counts", torch.int64, 2, 1)
+    positions = out_tensor(positions, "positions", torch.float32, cap_v, 3)
+    colors = out_tensor(colors, "colors", torch.uint8, cap_v, 3)
+    temperature = out_tensor(temperature, "temperature", torch.float32, cap_v, 1)
+    thermal_colors = out_tensor(thermal_colors, "thermal_colors", torch.uint8, cap_v, 3)
+    triangles = out_tensor(triangles, "triangles", torch.int32, cap_t, 3)
+    counts = out_tensor(counts, "counts", torch.int64, 2, 1)
     if cap_v > 0 and (positions is None or colors is None or temperature is None):
         raise ValueError("positions, colors and temperature are required when capacity_vertices > 0")
     if cap_t > 0 and triangles is None:
         raise ValueError("triangles are required when capacity_triangles > 0")
     if thermal_colors is not None:
-        t = thermal_table
-        if t is None or t.dtype != torch.uint8 or tuple(t.shape) != (256, 3) or not t.is_cuda or not t.is_contiguous():
-            raise ValueError("thermal_colors needs a contiguous uint8 [256, 3] device table")
-    need = mesh_workspace_bytes(params.dims)
-    if workspace is None:
-        workspace = torch.empty((need,), dtype=torch.uint8, device=v.device)
-    if not workspace.is_cuda or not workspace.is_contiguous() or workspace.numel() * workspace.element_size() < need:
-        raise ValueError(f"workspace must be a contiguous device tensor of at least {need} bytes")
+        check_color_table(thermal_table)
+    workspace, workspace_size = workspace_of(workspace, mesh_workspace_bytes(params.dims), v.device)
     with torch.cuda.device(v.device):
         _hip.check(_hip.load().tn_mesh_extract(
             v.data_ptr(), params, _hip.ptr(thermal_table) if thermal_colors is not None else None, _hip.ptr(positions),
             _hip.ptr(colors), _hip.ptr(temperature), _hip.ptr(thermal_colors), cap_v, _hip.ptr(triangles), cap_t, counts.data_ptr(),
-            workspace.data_ptr(), workspace.numel() * workspace.element_size(), _hip.current_stream()), "tn_mesh_extract")
+            workspace.data_ptr(), workspace_size, _hip.current_stream()), "tn_mesh_extract")
 
 
 @dataclass
@@ -221,8 +210,8 @@ def camera_pose(model, cameras, k: int, apply_camera_optimizer: bool = True) -> 
     return _compose(cameras.camera_to_worlds[int(k)], None if corr is None else corr[int(k)])
 
 
-class MeshExporter:
-    def __init__(self, model, *, max_temperature: float, min_temperature: float, resolution=256, bounding_box=_SCENE_BOX,
+class MeshExporter(PoseExporter):
+    def __init__(self, model, *, max_temperature: float, min_temperature: float, resolution=256, bounding_box=SCENE_BOX,
                  truncation: Optional[float] = None, min_accumulation: float = 0.5, depth_output_name: str = "depth",
                  thermal_color_map: str = "magma", to_world=None) -> None:
         """``model``: a fusable ThermalNerfModel in eval mode on a ROCm device.
@@ -236,70 +225,32 @@ class MeshExporter:
         ``depth_output_name``: "depth" (the median depth; default) or "expected_depth" (depends on the eval chunk size).
         ``thermal_color_map``: a name of ``colormaps.NAMES`` for ``thermal_colors``.
         ``to_world``: [3,4] applied to a vertex (``world_transform``); None: identity."""
-        if depth_output_name not in ("depth", "expected_depth"):
-            raise ValueError('depth_output_name must be "depth" or "expected_depth"')
-        if not model._fusable():
-            raise RuntimeError("MeshExporter drives the fused kernels through RayRenderEngine; this model is not fusable "
-                               "(staged field or non-default proposal structure)")
-        if isinstance(bounding_box, str) and bounding_box == _SCENE_BOX:
-            bounding_box = model.scene_box.aabb
-        if bounding_box is None:
+        super().__init__(model, depth_output_name, thermal_color_map, min_temperature, max_temperature)
+        box = resolve_box(model, bounding_box)
+        if box is None:
             raise ValueError("a mesh needs a bounding box: it is the extent of the voxel volume")
-        box = torch.as_tensor(bounding_box).detach().double().cpu().reshape(2, 3).tolist()
         self.dims = grid_dims(box[0], box[1], resolution)
         largest = max((box[1][c] - box[0][c]) / (self.dims[c] - 1) for c in range(3))
         if truncation is None:
             truncation = 4.0 * largest
         if not float(truncation) >= math.sqrt(3.0) * largest:
             raise ValueError(f"truncation {float(truncation):.6g} is below sqrt(3) x the largest grid step {largest:.6g}")
-        self.model = model
-        self.depth_output_name = depth_output_name
-        self.thermal_color_map = thermal_color_map
-        self.temperature_bounds = (float(min_temperature), float(max_temperature))
         self.truncation = float(truncation)
         self.params = mesh_params(box[0], box[1], self.dims, truncation, min_accumulation, max_temperature, min_temperature, to_world)
-        self._engine = None
         self.last_poses = 0  # poses fused by the last export
-
-    def _render(self, origins: Tensor, directions: Tensor, out):
-        from ..engine import RayRenderEngine
-
-        model = self.model
-        chunk = int(model.config.eval_num_rays_per_chunk)
-        eng = self._engine
-        if eng is None or eng.chunk != chunk or eng.rc.early_stop_transmittance != float(model.config.early_termination_eps):
-            eng = self._engine = RayRenderEngine(model, chunk=chunk)
-        eng.rc.pdf_anneal = float(model.proposal_sampler._anneal)
-        return eng.render(origins, directions, out=out)
 
     @torch.no_grad()
     def fuse(self, cameras, camera_indices: Optional[Sequence[int]] = None, apply_camera_optimizer: bool = True) -> Tensor:
         """Render ``cameras`` (all, or ``camera_indices``) and return the fused volume [7, Nz, Ny, Nx]; no host synchronisation
         after the pose table's one read."""
-        model = self.model
-        if model.training:
-            raise RuntimeError("MeshExporter renders in eval mode; call model.eval() first")
-        dev = torch.device(model.device)
-        if dev.type != "cuda":
-            raise RuntimeError(f"the model is on {dev}; thermo_nerf_amd exports only on a ROCm device (no CPU fallback exists)")
-        index = list(range(cameras.size)) if camera_indices is None else [int(k) for k in camera_indices]
-        if any(k < 0 or k >= cameras.size for k in index):
-            raise IndexError("camera index outside the camera set")
-        opt = model.camera_optimizer
-        adjust = bool(apply_camera_optimizer) and opt.config.mode != "off"
-        if adjust and any(k >= opt.num_cameras for k in index):
-            raise IndexError(f"the camera optimizer holds {opt.num_cameras} poses; pass apply_camera_optimizer=False for other views")
-        pinhole = dataclasses.replace(cameras, distortion_params=None)
-        corr = _corrections(opt) if adjust else None
+        dev, adjust, index, bundles = self._poses(cameras, camera_indices, apply_camera_optimizer, pinhole=True)
+        corr = _corrections(self.model.camera_optimizer) if adjust else None
         nx, ny, nz = self.dims
         self.last_poses = len(index)
         with torch.cuda.device(dev):
             volume = torch.zeros((PLANES, nz, ny, nx), dtype=torch.float32, device=dev)
             out = None
-            for k in index:
-                rb = pinhole.generate_rays(k, device=dev, flat=True)
-                if adjust:
-                    opt.apply_to_raybundle(rb)  # camera_indices = k for every ray of the pose
+            for k, rb in bundles:
                 out = self._render(rb.origins, rb.directions, out)
                 set_camera(self.params, float(cameras.fx[k]), float(cameras.fy[k]), float(cameras.cx), float(cameras.cy),
                            _compose(cameras.camera_to_worlds[k], None if corr is None else corr[k]))

@@ -12,6 +12,7 @@ import torch
 from torch import Tensor
 
 from .. import _hip
+from ._common import workspace_of
 from .pointcloud import ThermalPointCloud
 
 MAX_NEIGHBORS = 32  # tn_knn's largest k
@@ -64,13 +65,9 @@ def knn(positions: Tensor, k: int, *, grid_resolution: int = 0, indices: bool = 
         mean = torch.empty((n,), dtype=torch.float64, device=dev) if mean_distance else None
         if n == 0:
             return Neighbors(idx, d2, mean)
-        need = knn_workspace_bytes(n, res)
-        if workspace is None:
-            workspace = torch.empty((need,), dtype=torch.uint8, device=dev)
-        if not workspace.is_cuda or not workspace.is_contiguous() or workspace.numel() * workspace.element_size() < need:
-            raise ValueError(f"workspace must be a contiguous device tensor of at least {need} bytes")
+        workspace, workspace_size = workspace_of(workspace, knn_workspace_bytes(n, res), dev)
         _hip.check(_hip.load().tn_knn(p.data_ptr(), n, k, res, _hip.ptr(idx), _hip.ptr(d2), _hip.ptr(mean), workspace.data_ptr(),
-                                      workspace.numel() * workspace.element_size(), _hip.current_stream()), "tn_knn")
+                                      workspace_size, _hip.current_stream()), "tn_knn")
     return Neighbors(idx, d2, mean)
 
 

@@ -55,50 +55,75 @@ def _host(t) -> np.ndarray:
     return t.detach().cpu().numpy() if hasattr(t, "detach") else np.asarray(t)
 
 
+def _vertex_array(obj, colors: str, dtype, no_thermal: str, disagree: str) -> np.ndarray:
+    """the vertex records of a cloud or a mesh (x y z, red green blue, temperature filled), after the checks both writers make"""
+    if colors not in ("rgb", "thermal"):
+        raise ValueError('colors must be "rgb" or "thermal"')
+    col = obj.colors if colors == "rgb" else obj.thermal_colors
+    if col is None:
+        raise ValueError(no_thermal)
+    pos, col, temp = _host(obj.positions), _host(col), _host(obj.temperature)
+    m = pos.shape[0]
+    if pos.shape != (m, 3) or col.shape != (m, 3) or temp.shape != (m,):
+        raise ValueError(disagree)
+    vertex = np.empty(m, dtype=dtype)
+    vertex["x"], vertex["y"], vertex["z"] = pos[:, 0], pos[:, 1], pos[:, 2]
+    vertex["red"], vertex["green"], vertex["blue"] = col[:, 0], col[:, 1], col[:, 2]
+    vertex["temperature"] = temp
+    return vertex
+
+
+def _write(path, head: str, *arrays: np.ndarray) -> Path:
+    path = Path(path)
+    path.parent.mkdir(parents=True, exist_ok=True)
+    with open(path, "wb") as f:
+        f.write(head.encode("ascii"))
+        for a in arrays:
+            a.tofile(f)
+    return path
+
+
+def _read_header(path):
+    """(the file's bytes, the offset of its body, the header's lines, its comment lines without the keyword)"""
+    blob = Path(path).read_bytes()
+    end = blob.find(b"end_header\n")
+    if not blob.startswith(b"ply\n") or end < 0:
+        raise ValueError(f"{path}: not a PLY file")
+    lines = blob[:end].decode("ascii").split("\n")
+    if lines[1] != "format binary_little_endian 1.0":
+        raise ValueError(f"{path}: only binary little-endian PLY is read")
+    return blob, end + len(b"end_header\n"), lines, [ln[len("comment "):] for ln in lines if ln.startswith("comment ")]
+
+
+def _vertex_fields(vertex: np.ndarray, comments) -> Dict:
+    m = vertex.shape[0]
+    return {"positions": np.stack([vertex["x"], vertex["y"], vertex["z"]], axis=1) if m else np.zeros((0, 3), np.float32),
+            "colors": np.stack([vertex["red"], vertex["green"], vertex["blue"]], axis=1) if m else np.zeros((0, 3), np.uint8),
+            "temperature": vertex["temperature"].copy(), "comments": comments}
+
+
 def write_ply(path, cloud, colors: str = "rgb") -> Path:
     """Write ``cloud`` (a ThermalPointCloud, on the device or the host) to ``path``.  ``colors``: which bytes fill red / green /
     blue — "rgb" (the rendered colours) or "thermal" (the colour-mapped temperature).  ``cloud.normals``, where set, are written
     as nx ny nz behind z.  One device -> host copy per array."""
-    if colors not in ("rgb", "thermal"):
-        raise ValueError('colors must be "rgb" or "thermal"')
-    col = cloud.colors if colors == "rgb" else cloud.thermal_colors
-    if col is None:
-        raise ValueError("the cloud holds no thermal colours (exported without a colour table)")
-    pos, col, temp = _host(cloud.positions), _host(col), _host(cloud.temperature)
-    m = pos.shape[0]
-    if pos.shape != (m, 3) or col.shape != (m, 3) or temp.shape != (m,):
-        raise ValueError("positions [M,3], colours [M,3] and temperature [M] must agree")
     normals = getattr(cloud, "normals", None)
-    vertex = np.empty(m, dtype=VERTEX_DTYPE if normals is None else NORMAL_VERTEX_DTYPE)
-    vertex["x"], vertex["y"], vertex["z"] = pos[:, 0], pos[:, 1], pos[:, 2]
-    vertex["red"], vertex["green"], vertex["blue"] = col[:, 0], col[:, 1], col[:, 2]
-    vertex["temperature"] = temp
+    vertex = _vertex_array(cloud, colors, VERTEX_DTYPE if normals is None else NORMAL_VERTEX_DTYPE,
+                           "the cloud holds no thermal colours (exported without a colour table)",
+                           "positions [M,3], colours [M,3] and temperature [M] must agree")
+    m = vertex.shape[0]
     if normals is not None:
         nrm = _host(normals)
         if nrm.shape != (m, 3):
             raise ValueError("normals must be [M,3]")
         vertex["nx"], vertex["ny"], vertex["nz"] = nrm[:, 0], nrm[:, 1], nrm[:, 2]
-    path = Path(path)
-    path.parent.mkdir(parents=True, exist_ok=True)
-    with open(path, "wb") as f:
-        f.write(header(m, getattr(cloud, "temperature_bounds", None), normals is not None).encode("ascii"))
-        vertex.tofile(f)
-    return path
+    return _write(path, header(m, getattr(cloud, "temperature_bounds", None), normals is not None), vertex)
 
 
 def read_ply(path) -> Dict:
     """The arrays of a file ``write_ply`` wrote: ``positions`` float32 [M,3], ``colors`` uint8 [M,3], ``temperature`` float32 [M],
     ``comments`` (the header's comment lines without the keyword), and ``normals`` float32 [M,3] when the file carries them (the
     31-byte layout).  M = 0 — a header without a body — is a valid file."""
-    blob = Path(path).read_bytes()
-    end = blob.find(b"end_header\n")
-    if not blob.startswith(b"ply\n") or end < 0:
-        raise ValueError(f"{path}: not a PLY file")
-    body = end + len(b"end_header\n")
-    lines = blob[:end].decode("ascii").split("\n")
-    if lines[1] != "format binary_little_endian 1.0":
-        raise ValueError(f"{path}: only binary little-endian PLY is read")
-    comments = [ln[len("comment "):] for ln in lines if ln.startswith("comment ")]
+    blob, body, lines, comments = _read_header(path)
     counts = [ln for ln in lines if ln.startswith("element ")]
     if len(counts) != 1 or not counts[0].startswith("element vertex "):
         raise ValueError(f"{path}: one vertex element expected")
@@ -110,9 +135,7 @@ def read_ply(path) -> Dict:
     if len(blob) - body != m * dtype.itemsize:
         raise ValueError(f"{path}: {len(blob) - body} body bytes for {m} vertices of {dtype.itemsize} bytes")
     vertex = np.frombuffer(blob, dtype=dtype, count=m, offset=body)
-    out = {"positions": np.stack([vertex["x"], vertex["y"], vertex["z"]], axis=1) if m else np.zeros((0, 3), np.float32),
-           "colors": np.stack([vertex["red"], vertex["green"], vertex["blue"]], axis=1) if m else np.zeros((0, 3), np.uint8),
-           "temperature": vertex["temperature"].copy(), "comments": comments}
+    out = _vertex_fields(vertex, comments)
     if dtype is NORMAL_VERTEX_DTYPE:
         out["normals"] = np.stack([vertex["nx"], vertex["ny"], vertex["nz"]], axis=1) if m else np.zeros((0, 3), np.float32)
     return out
@@ -135,43 +158,23 @@ def mesh_header(num_vertices: int, num_triangles: int, temperature_bounds=None) 
 def write_mesh_ply(path, mesh, colors: str = "rgb") -> Path:
     """Write ``mesh`` (a ThermalMesh, on the device or the host) to ``path``; ``colors`` as in ``write_ply``.  V = 0 or T = 0 is a
     valid file.  One device -> host copy per array."""
-    if colors not in ("rgb", "thermal"):
-        raise ValueError('colors must be "rgb" or "thermal"')
-    col = mesh.colors if colors == "rgb" else mesh.thermal_colors
-    if col is None:
-        raise ValueError("the mesh holds no thermal colours (extracted without a colour table)")
-    pos, col, temp, tri = _host(mesh.positions), _host(col), _host(mesh.temperature), _host(mesh.triangles)
-    m, t = pos.shape[0], tri.shape[0]
-    if pos.shape != (m, 3) or col.shape != (m, 3) or temp.shape != (m,) or tri.shape != (t, 3):
-        raise ValueError("positions [V,3], colours [V,3], temperature [V] and triangles [T,3] must agree")
+    disagree = "positions [V,3], colours [V,3], temperature [V] and triangles [T,3] must agree"
+    vertex = _vertex_array(mesh, colors, VERTEX_DTYPE, "the mesh holds no thermal colours (extracted without a colour table)", disagree)
+    tri = _host(mesh.triangles)
+    m, t = vertex.shape[0], tri.shape[0]
+    if tri.shape != (t, 3):
+        raise ValueError(disagree)
     if t and (tri.min() < 0 or tri.max() >= m):
         raise ValueError("a triangle names a vertex outside [0, V)")
-    vertex = np.empty(m, dtype=VERTEX_DTYPE)
-    vertex["x"], vertex["y"], vertex["z"] = pos[:, 0], pos[:, 1], pos[:, 2]
-    vertex["red"], vertex["green"], vertex["blue"] = col[:, 0], col[:, 1], col[:, 2]
-    vertex["temperature"] = temp
     face = np.empty(t, dtype=FACE_DTYPE)
     face["n"], face["v"] = 3, tri
-    path = Path(path)
-    path.parent.mkdir(parents=True, exist_ok=True)
-    with open(path, "wb") as f:
-        f.write(mesh_header(m, t, getattr(mesh, "temperature_bounds", None)).encode("ascii"))
-        vertex.tofile(f)
-        face.tofile(f)
-    return path
+    return _write(path, mesh_header(m, t, getattr(mesh, "temperature_bounds", None)), vertex, face)
 
 
 def read_mesh_ply(path) -> Dict:
     """The arrays of a file ``write_mesh_ply`` wrote: ``read_ply``'s ``positions`` / ``colors`` / ``temperature`` / ``comments`` and
     ``triangles`` int32 [T,3]."""
-    blob = Path(path).read_bytes()
-    end = blob.find(b"end_header\n")
-    if not blob.startswith(b"ply\n") or end < 0:
-        raise ValueError(f"{path}: not a PLY file")
-    body = end + len(b"end_header\n")
-    lines = blob[:end].decode("ascii").split("\n")
-    if lines[1] != "format binary_little_endian 1.0":
-        raise ValueError(f"{path}: only binary little-endian PLY is read")
+    blob, body, lines, comments = _read_header(path)
     counts = [ln.split() for ln in lines if ln.startswith("element ")]
     if [c[1] for c in counts] != ["vertex", "face"]:
         raise ValueError(f"{path}: a vertex element and a face element expected")
@@ -184,7 +187,4 @@ def read_mesh_ply(path) -> Dict:
     face = np.frombuffer(blob, dtype=FACE_DTYPE, count=t, offset=body + m * VERTEX_DTYPE.itemsize)
     if t and not (face["n"] == 3).all():
         raise ValueError(f"{path}: only triangles are read")
-    return {"positions": np.stack([vertex["x"], vertex["y"], vertex["z"]], axis=1) if m else np.zeros((0, 3), np.float32),
-            "colors": np.stack([vertex["red"], vertex["green"], vertex["blue"]], axis=1) if m else np.zeros((0, 3), np.uint8),
-            "temperature": vertex["temperature"].copy(), "triangles": face["v"].astype(np.int32).reshape(t, 3),
-            "comments": [ln[len("comment "):] for ln in lines if ln.startswith("comment ")]}
+    return {**_vertex_fields(vertex, comments), "triangles": face["v"].astype(np.int32).reshape(t, 3)}

@@ -17,10 +17,9 @@ import torch
 from torch import Tensor
 
 from .. import _hip, colormaps
+from ._common import SCENE_BOX, PoseExporter, affine12, check_color_table, out_tensor, resolve_box, workspace_of
 
-_SCENE_BOX = "scene_box"
 _INF = float("inf")
-_IDENTITY = (1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0)
 
 
 def tile_rays() -> int:
@@ -49,20 +48,8 @@ def pointcloud_params(min_accumulation: float = 0.5, box_min: Sequence[float] = 
     q.thermal_lo, q.thermal_hi = float(thermal_lo), float(thermal_hi)
     q.temperature_span = float(max_temperature) - float(min_temperature)
     q.temperature_min = float(min_temperature)
-    m = _IDENTITY if to_world is None else tuple(float(v) for v in np.asarray(to_world, dtype=np.float64).reshape(-1))
-    if len(m) != 12:
-        raise ValueError("to_world is a 3 x 4 matrix")
-    for k in range(12):
-        q.to_world[k] = m[k]
+    q.to_world[:] = affine12(to_world)
     return q
-
-
-def _out(t: Optional[Tensor], name: str, dtype: torch.dtype, capacity: int, width: int) -> Optional[Tensor]:
-    if t is None:
-        return None
-    if not isinstance(t, Tensor) or not t.is_cuda or t.dtype != dtype or not t.is_contiguous() or t.numel() < capacity * width:
-        raise ValueError(f"{name} must be a contiguous {dtype} device tensor of at least {capacity * width} elements")
-    return t
 
 
 def pointcloud_append(origins: Tensor, directions: Tensor, depth: Tensor, accumulation: Tensor, rgb: Tensor, thermal: Tensor,
@@ -91,29 +78,23 @@ def pointcloud_append(origins: Tensor, directions: Tensor, depth: Tensor, accumu
     capacity = int(capacity)
     if capacity < 0:
         raise ValueError("capacity must not be negative")
-    positions = _out(positions, "positions", torch.float32, capacity, 3)
-    colors = _out(colors, "colors", torch.uint8, capacity, 3)
-    temperature = _out(temperature, "temperature", torch.float32, capacity, 1)
-    thermal_colors = _out(thermal_colors, "thermal_colors", torch.uint8, capacity, 3)
-    source = _out(source, "source", torch.int64, capacity, 1)
-    count = _out(count, "count", torch.int64, 1, 1)
+    positions = out_tensor(positions, "positions", torch.float32, capacity, 3)
+    colors = out_tensor(colors, "colors", torch.uint8, capacity, 3)
+    temperature = out_tensor(temperature, "temperature", torch.float32, capacity, 1)
+    thermal_colors = out_tensor(thermal_colors, "thermal_colors", torch.uint8, capacity, 3)
+    source = out_tensor(source, "source", torch.int64, capacity, 1)
+    count = out_tensor(count, "count", torch.int64, 1, 1)
     if thermal_colors is not None:
-        t = thermal_table
-        if t is None or t.dtype != torch.uint8 or tuple(t.shape) != (256, 3) or not t.is_cuda or not t.is_contiguous():
-            raise ValueError("thermal_colors needs a contiguous uint8 [256, 3] device table")
+        check_color_table(thermal_table)
     if n == 0:
         return
-    need = workspace_bytes(n)
-    if workspace is None:
-        workspace = torch.empty((need,), dtype=torch.uint8, device=o.device)
-    if not workspace.is_cuda or not workspace.is_contiguous() or workspace.numel() * workspace.element_size() < need:
-        raise ValueError(f"workspace must be a contiguous device tensor of at least {need} bytes")
+    workspace, workspace_size = workspace_of(workspace, workspace_bytes(n), o.device)
     with torch.cuda.device(o.device):
         _hip.check(_hip.load().tn_pointcloud_append(
             o.data_ptr(), d.data_ptr(), per_ray[0].data_ptr(), per_ray[1].data_ptr(), c.data_ptr(), per_ray[2].data_ptr(), n,
             int(source_base), params, _hip.ptr(thermal_table) if thermal_colors is not None else None, positions.data_ptr(),
             colors.data_ptr(), temperature.data_ptr(), _hip.ptr(thermal_colors), _hip.ptr(source), capacity, count.data_ptr(),
-            workspace.data_ptr(), workspace.numel() * workspace.element_size(), _hip.current_stream()), "tn_pointcloud_append")
+            workspace.data_ptr(), workspace_size, _hip.current_stream()), "tn_pointcloud_append")
 
 
 @dataclass
@@ -173,9 +154,9 @@ def world_transform(dataparser_outputs) -> Tensor:
     return torch.from_numpy(m.astype(np.float32))
 
 
-class PointCloudExporter:
+class PointCloudExporter(PoseExporter):
     def __init__(self, model, *, max_temperature: float, min_temperature: float, depth_output_name: str = "depth",
-                 min_accumulation: float = 0.5, bounding_box=_SCENE_BOX, threshold: Optional[float] = None, cold: bool = False,
+                 min_accumulation: float = 0.5, bounding_box=SCENE_BOX, threshold: Optional[float] = None, cold: bool = False,
                  thermal_color_map: str = "magma", to_world=None) -> None:
         """``model``: a fusable ThermalNerfModel in eval mode on a ROCm device.
         ``max_temperature`` / ``min_temperature``: the degrees of normalised thermal 1 and 0 (``mae_thermal``'s de-normalisation).
@@ -188,42 +169,17 @@ class PointCloudExporter:
         applies to ground truth; None: no thermal cut.
         ``thermal_color_map``: a name of ``colormaps.NAMES`` for ``thermal_colors``.
         ``to_world``: [3,4] applied to a kept point AFTER the box test (``world_transform``); None: identity."""
-        if depth_output_name not in ("depth", "expected_depth"):
-            raise ValueError('depth_output_name must be "depth" or "expected_depth"')
-        if not model._fusable():
-            raise RuntimeError("PointCloudExporter drives the fused kernels through RayRenderEngine; this model is not fusable "
-                               "(staged field or non-default proposal structure)")
-        self.model = model
-        self.depth_output_name = depth_output_name
-        self.thermal_color_map = thermal_color_map
-        self.temperature_bounds = (float(min_temperature), float(max_temperature))
-        if isinstance(bounding_box, str) and bounding_box == _SCENE_BOX:
-            bounding_box = model.scene_box.aabb
-        if bounding_box is None:
-            box = [[-_INF] * 3, [_INF] * 3]
-        else:
-            box = torch.as_tensor(bounding_box).detach().double().cpu().reshape(2, 3).tolist()
+        super().__init__(model, depth_output_name, thermal_color_map, min_temperature, max_temperature)
+        box = resolve_box(model, bounding_box) or [[-_INF] * 3, [_INF] * 3]
         lo, hi = -_INF, _INF
         if threshold is not None:
             if math.isnan(float(threshold)):
                 raise ValueError("threshold is NaN")
             lo, hi = (-_INF, float(threshold)) if cold else (float(threshold), _INF)
         self.params = pointcloud_params(min_accumulation, box[0], box[1], lo, hi, max_temperature, min_temperature, to_world)
-        self._engine = None
         self.last_rays = 0  # rays cast by the last export
         self.camera_viewpoints = None  # float32 [cameras.size, 3] on the device: where the last export's cameras stood (NaN rows: not rendered)
         self._rays_per_camera = 0
-
-    def _render(self, origins: Tensor, directions: Tensor, out):
-        from ..engine import RayRenderEngine
-
-        model = self.model
-        chunk = int(model.config.eval_num_rays_per_chunk)
-        eng = self._engine
-        if eng is None or eng.chunk != chunk or eng.rc.early_stop_transmittance != float(model.config.early_termination_eps):
-            eng = self._engine = RayRenderEngine(model, chunk=chunk)
-        eng.rc.pdf_anneal = float(model.proposal_sampler._anneal)
-        return eng.render(origins, directions, out=out)
 
     @torch.no_grad()
     def export(self, cameras, camera_indices: Optional[Sequence[int]] = None, apply_camera_optimizer: bool = True,
@@ -232,19 +188,7 @@ class PointCloudExporter:
         ``apply_camera_optimizer``: adjust camera k's rays with row k of the model's pose table — right for the TRAINING
         cameras, whose corrected poses the field was fitted to (pass False for other views).  ``max_points``: the buffers'
         capacity (default: every ray); a cloud that outgrows it raises with both numbers.  One host read at the end."""
-        model = self.model
-        if model.training:
-            raise RuntimeError("PointCloudExporter renders in eval mode; call model.eval() first")
-        dev = torch.device(model.device)
-        if dev.type != "cuda":
-            raise RuntimeError(f"the model is on {dev}; thermo_nerf_amd exports only on a ROCm device (no CPU fallback exists)")
-        index = list(range(cameras.size)) if camera_indices is None else [int(k) for k in camera_indices]
-        if any(k < 0 or k >= cameras.size for k in index):
-            raise IndexError("camera index outside the camera set")
-        opt = model.camera_optimizer
-        adjust = bool(apply_camera_optimizer) and opt.config.mode != "off"
-        if adjust and any(k >= opt.num_cameras for k in index):
-            raise IndexError(f"the camera optimizer holds {opt.num_cameras} poses; pass apply_camera_optimizer=False for other views")
+        dev, _, index, bundles = self._poses(cameras, camera_indices, apply_camera_optimizer)
         n = cameras.height * cameras.width
         self.last_rays = n * len(index)
         capacity = self.last_rays if max_points is None else int(max_points)
@@ -262,10 +206,7 @@ class PointCloudExporter:
             viewpoints = torch.full((cameras.size, 3), float("nan"), dtype=torch.float32, device=dev)
             to_world = torch.tensor(list(self.params.to_world), dtype=torch.float32, device=dev).reshape(3, 4)
             out = None
-            for k in index:
-                rb = cameras.generate_rays(k, device=dev, flat=True)
-                if adjust:
-                    opt.apply_to_raybundle(rb)  # camera_indices = k for every ray of the pose
+            for k, rb in bundles:
                 viewpoints[k] = to_world[:, :3] @ rb.origins[0] + to_world[:, 3]  # the corrected pose's centre, as the points are mapped
                 out = self._render(rb.origins, rb.directions, out)
                 pointcloud_append(rb.origins, rb.directions, out[self.depth_output_name], out["accumulation"], out["rgb"],

@@ -118,13 +118,9 @@ class Renderer:
             h, w = cameras.height, cameras.width
             res = model.get_outputs_for_camera_ray_bundle(RayBundle(origins=rb.origins.view(h, w, 3), directions=rb.directions.view(h, w, 3)))
             return {k: v.reshape(h * w, -1) for k, v in res.items()}, None
-        from ..engine import RayRenderEngine
+        from ..engine import engine_for
 
-        chunk = int(model.config.eval_num_rays_per_chunk)
-        eng = self._engine
-        if eng is None or eng.chunk != chunk or eng.rc.early_stop_transmittance != float(model.config.early_termination_eps):
-            eng = self._engine = RayRenderEngine(model, chunk=chunk)
-        eng.rc.pdf_anneal = float(model.proposal_sampler._anneal)
+        eng = self._engine = engine_for(model, self._engine)
         eng.timings.clear()
         out = eng.render(rb.origins, rb.directions, out=out, record_events=True)
         gate = eng.timings[0][1] if eng.timings else None

@@ -89,3 +89,33 @@ def evaluate_run(run_dir, data, config, num_train_data: int, eval_mode: str = "f
     renderer = Renderer.from_checkpoint(run_dir, config, num_train_data, device=device, scene_box=eval_out.scene_box)
     return Evaluator(renderer.model, ThermalDataset(eval_out), experiment_name=experiment_name, modalities_to_save=list(modalities),
                      threshold=threshold, device=device)
+
+
+def load_run_for_export(args) -> Dict:
+    """What an export command line starts from.  ``args``: ``model_uri``, ``dataset_path``, ``split``, ``config_json``,
+    ``resolution_scale``, ``device``, ``bounding_box_min`` / ``bounding_box_max`` and, optionally, ``no_bounding_box``.  Returns
+    ``run`` (the run's config.json), ``parsed`` (the split's dataparser outputs), ``model`` (the newest checkpoint, eval mode, on
+    the device), ``cameras`` (the split's, rescaled), ``max_temperature`` / ``min_temperature`` and ``bounding_box`` (the explicit
+    one, None with ``no_bounding_box``, else the dataset's scene box)."""
+    from .data import ThermalDataParserConfig
+    from .render import Renderer
+
+    run = read_run_config(args.model_uri)
+    over = dict(run.get("model", {}))
+    over.update(load_overrides(args.config_json))
+    parsed = ThermalDataParserConfig(data=Path(args.dataset_path), eval_mode=run.get("eval_mode", "filename")).setup() \
+        .get_dataparser_outputs(args.split)
+    renderer = Renderer.from_checkpoint(args.model_uri, model_config(over), int(run["num_train_data"]), device=args.device,
+                                        scene_box=parsed.scene_box)
+    cameras = parsed.cameras
+    if args.resolution_scale != 1.0:
+        cameras.rescale_output_resolution(args.resolution_scale)
+    max_t, min_t = (float(v) for v in run["temperature_bounds"])
+    if getattr(args, "no_bounding_box", False):
+        box = None
+    elif args.bounding_box_min is not None:
+        box = [args.bounding_box_min, args.bounding_box_max]
+    else:
+        box = parsed.scene_box.aabb
+    return dict(run=run, parsed=parsed, model=renderer.model, cameras=cameras, max_temperature=max_t, min_temperature=min_t,
+                bounding_box=box)

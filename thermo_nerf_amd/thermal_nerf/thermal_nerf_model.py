@@ -186,16 +186,13 @@ class ThermalNerfModel(ThermalNerfactoModel):
         alternating HIP streams; otherwise the generic per-chunk loop runs."""
         if self.training or not self._fusable():
             return super().get_outputs_for_camera_ray_bundle(camera_ray_bundle)
-        from ..engine import RayRenderEngine
+        from ..engine import engine_for
 
-        chunk = int(self.config.eval_num_rays_per_chunk)
-        eng = _ENGINES.get(self)  # side table: streams / ctypes structs must not ride along in deepcopy / state_dict
-        if eng is None or eng.chunk != chunk or eng.rc.early_stop_transmittance != float(self.config.early_termination_eps):
-            eng = _ENGINES[self] = RayRenderEngine(weakref.proxy(self), chunk=chunk)  # proxy: the table must not keep the model alive
+        # side table: streams / ctypes structs must not ride along in deepcopy / state_dict; proxy: it must not keep the model alive
+        eng = _ENGINES[self] = engine_for(weakref.proxy(self), _ENGINES.get(self))
         h, w = camera_ray_bundle.origins.shape[:2]
         o = camera_ray_bundle.origins.reshape(-1, 3).to(self.device)
         d = camera_ray_bundle.directions.reshape(-1, 3).to(self.device)
-        eng.rc.pdf_anneal = float(self.proposal_sampler._anneal)
         nears, fars = camera_ray_bundle.nears, camera_ray_bundle.fars
         if nears is not None and fars is not None:  # planes already on the bundle win over the collider's constants
             nears, fars = nears.reshape(-1).to(self.device), fars.reshape(-1).to(self.device)

@@ -55,29 +55,16 @@ def parse(argv=None) -> argparse.Namespace:
 def build_exporter(args):
     """(exporter, cameras of the split, apply_camera_optimizer) as ``main`` sets them up — also what a caller that wants the mesh
     in-process uses"""
-    from thermo_nerf_amd import run_config
-    from thermo_nerf_amd.data import ThermalDataParserConfig
     from thermo_nerf_amd.export import MeshExporter, world_transform
-    from thermo_nerf_amd.render import Renderer
+    from thermo_nerf_amd.run_config import load_run_for_export
 
-    run = run_config.read_run_config(args.model_uri)
-    over = dict(run.get("model", {}))
-    over.update(run_config.load_overrides(args.config_json))
-    config = run_config.model_config(over)
-    parsed = ThermalDataParserConfig(data=Path(args.dataset_path), eval_mode=run.get("eval_mode", "filename")).setup() \
-        .get_dataparser_outputs(args.split)
-    renderer = Renderer.from_checkpoint(args.model_uri, config, int(run["num_train_data"]), device=args.device,
-                                        scene_box=parsed.scene_box)
-    cameras = parsed.cameras
-    if args.resolution_scale != 1.0:
-        cameras.rescale_output_resolution(args.resolution_scale)
-    max_t, min_t = (float(v) for v in run["temperature_bounds"])
-    box = [args.bounding_box_min, args.bounding_box_max] if args.bounding_box_min is not None else parsed.scene_box.aabb
+    r = load_run_for_export(args)
     resolution = args.resolution[0] if len(args.resolution) == 1 else tuple(args.resolution)
-    exporter = MeshExporter(renderer.model, max_temperature=max_t, min_temperature=min_t, resolution=resolution, bounding_box=box,
-                            truncation=args.truncation, min_accumulation=args.min_accumulation, depth_output_name=args.depth,
-                            to_world=None if args.scene_frame else world_transform(parsed))
-    return exporter, cameras, args.split == "train"
+    exporter = MeshExporter(r["model"], max_temperature=r["max_temperature"], min_temperature=r["min_temperature"],
+                            resolution=resolution, bounding_box=r["bounding_box"], truncation=args.truncation,
+                            min_accumulation=args.min_accumulation, depth_output_name=args.depth,
+                            to_world=None if args.scene_frame else world_transform(r["parsed"]))
+    return exporter, r["cameras"], args.split == "train"
 
 
 def main(argv=None) -> int:

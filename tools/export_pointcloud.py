@@ -88,39 +88,20 @@ def parse(argv=None) -> argparse.Namespace:
 def build_exporter(args):
     """(exporter, cameras of the split, apply_camera_optimizer) as ``main`` sets them up — also what a caller that wants the cloud
     in-process uses"""
-    from thermo_nerf_amd import run_config
-    from thermo_nerf_amd.data import ThermalDataParserConfig
     from thermo_nerf_amd.export import PointCloudExporter, world_transform
     from thermo_nerf_amd.model_type import ModelType
-    from thermo_nerf_amd.render import Renderer
+    from thermo_nerf_amd.run_config import load_run_for_export
     from thermo_nerf_amd.thermal_nerf.calculate_threshold import calculate_threshold
 
-    run = run_config.read_run_config(args.model_uri)
-    over = dict(run.get("model", {}))
-    over.update(run_config.load_overrides(args.config_json))
-    config = run_config.model_config(over)
-    parsed = ThermalDataParserConfig(data=Path(args.dataset_path), eval_mode=run.get("eval_mode", "filename")).setup() \
-        .get_dataparser_outputs(args.split)
-    renderer = Renderer.from_checkpoint(args.model_uri, config, int(run["num_train_data"]), device=args.device,
-                                        scene_box=parsed.scene_box)
-    cameras = parsed.cameras
-    if args.resolution_scale != 1.0:
-        cameras.rescale_output_resolution(args.resolution_scale)
+    r = load_run_for_export(args)
     threshold = args.threshold
     if threshold == "auto":
         threshold = calculate_threshold(args.dataset_path, ModelType.THERMONERF, device=args.device)
-    max_t, min_t = (float(v) for v in run["temperature_bounds"])
-    if args.no_bounding_box:
-        box = None
-    elif args.bounding_box_min is not None:
-        box = [args.bounding_box_min, args.bounding_box_max]
-    else:
-        box = parsed.scene_box.aabb
-    exporter = PointCloudExporter(renderer.model, max_temperature=max_t, min_temperature=min_t, depth_output_name=args.depth,
-                                  min_accumulation=args.min_accumulation, bounding_box=box, threshold=threshold,
-                                  cold=bool(run.get("cold", False)),
-                                  to_world=None if args.scene_frame else world_transform(parsed))
-    return exporter, cameras, args.split == "train"
+    exporter = PointCloudExporter(r["model"], max_temperature=r["max_temperature"], min_temperature=r["min_temperature"],
+                                  depth_output_name=args.depth, min_accumulation=args.min_accumulation,
+                                  bounding_box=r["bounding_box"], threshold=threshold, cold=bool(r["run"].get("cold", False)),
+                                  to_world=None if args.scene_frame else world_transform(r["parsed"]))
+    return exporter, r["cameras"], args.split == "train"
 
 
 def main(argv=None) -> int:
