@@ -415,6 +415,51 @@ int tn_mesh_extract(const float *volume, const tn_mesh_params *params, const uin
                     uint8_t *colors, float *temperature, uint8_t *thermal_colors, int64_t capacity_vertices, int32_t *triangles,
                     int64_t capacity_triangles, int64_t *counts, void *workspace, size_t workspace_bytes, void *stream);
 
+/* Connected components of an indexed triangle list and the removal of small ones (what a viewer's "remove small connected
+ * components" does to the islands a TSDF volume makes of floaters).  triangles: [T, 3] device int32, V = num_vertices,
+ * T = num_triangles.  Every output is an integer defined to the bit.
+ *   A triangle is VALID iff its three indices are all in [0, V).  An invalid triangle connects nothing and is never emitted; a
+ *   valid one with a repeated index still connects and is still counted.
+ *   Two vertices are CONNECTED iff a chain of valid triangles joins them, consecutive triangles sharing at least ONE vertex: this
+ *   is vertex connectivity, not edge adjacency — a floater that touches the wall at one vertex is part of the wall — and it is
+ *   what an indexed list makes cheap (a triangle unites its three indices; no edge table).
+ * tn_mesh_components:
+ *   labels[v] (int32 [V]): the smallest vertex index in v's component; a vertex in no valid triangle is its own component.
+ *   component_triangles[r] (int32 [V]): where labels[r] == r, the number of valid triangles whose FIRST index has label r; 0 at
+ *   every other r.
+ *   summary (device int64 [3], OVERWRITTEN): [0] the number of components (labels[v] == v), isolated vertices included; [1] the
+ *   largest component_triangles value; [2] the label that holds it, the lowest label on a tie.  With T == 0 or no valid triangle
+ *   [1] is 0 and [2] is 0.
+ * tn_mesh_filter_components, on the three outputs above.  A component is KEPT iff
+ *     component_triangles[label] >= max(min_triangles, 1)   and   (largest_only == 0 or label == summary[2])
+ *   (summary is read on the device; it may be NULL iff largest_only == 0).  A vertex is kept iff its component is — a vertex in no
+ *   triangle therefore always goes —, a triangle iff it is valid and its component is kept.
+ *   vertex_source (int32 [capacity_vertices]): the old indices of the kept vertices, ascending.
+ *   triangles_out (int32 [capacity_triangles, 3]): the kept triangles in their input order, every index rewritten to its rank among
+ *   the kept vertices.
+ *   counts (device int64 [2], OVERWRITTEN): the full numbers of kept vertices and kept triangles; writes happen only below the
+ *   capacities (both 0 with NULL outputs: the sizing call).
+ *   workspace: tn_mesh_components_workspace_bytes(V, T) bytes, 8-byte aligned; its first int32 per vertex is vertex_map (the new
+ *   index or -1).
+ * Labelling is a lock-free union-find (hook with compare-and-swap of the higher root under the lower, path halving), then a
+ * flatten pass; thermo_nerf_amd/csrc/tn_mesh_components.hip and DESIGN.md state why it ends and why the labels do not depend on
+ * the schedule.  At most six launches each on `stream` (tn_mesh_components: init, hook, flatten, count, summarise, unpack; the
+ * filter: count, one-block scan, emit, twice, with the tile and scan widths of tn_mesh_tile / tn_mesh_scan_width), no host
+ * synchronisation, no allocation.  Integer atomics only (compare-and-swap, add, a 64-bit max of (count << 32) | (0x7fffffff -
+ * label)); no block waits for another, and nothing in any output depends on the order of arrival.
+ * TN_ERR_NULL: a required pointer is NULL (summary of tn_mesh_components and counts always; labels, component_triangles and the
+ * workspace when V > 0; triangles when T > 0; an output when its capacity > 0; summary with largest_only); TN_ERR_SHAPE: V or T
+ * negative or above 2^31 - 1, a negative capacity or min_triangles, a misaligned pointer; TN_ERR_WORKSPACE: workspace_bytes too
+ * small.  All are returned before any launch.  V == 0: TN_OK, summary / counts are zeroed by a memset, nothing else is launched.
+ * T == 0 with V > 0: every vertex is its own label.  tn_mesh_components_workspace_bytes is 0 for counts out of range. */
+size_t tn_mesh_components_workspace_bytes(int64_t num_vertices, int64_t num_triangles);
+int tn_mesh_components(const int32_t *triangles, int64_t num_triangles, int64_t num_vertices, int32_t *labels,
+                       int32_t *component_triangles, int64_t *summary, void *stream);
+int tn_mesh_filter_components(const int32_t *triangles, int64_t num_triangles, int64_t num_vertices, const int32_t *labels,
+                              const int32_t *component_triangles, const int64_t *summary, int64_t min_triangles,
+                              int32_t largest_only, int32_t *vertex_source, int64_t capacity_vertices, int32_t *triangles_out,
+                              int64_t capacity_triangles, int64_t *counts, void *workspace, size_t workspace_bytes, void *stream);
+
 /* ------------------------------------------------------------------------------------------------------
  * Fused forward: Model.forward (collider) + ThermalNerfModel.get_outputs
  * [REF thermal_nerf_model.py:210-275]

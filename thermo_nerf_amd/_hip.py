@@ -235,6 +235,9 @@ SIGNATURES = {
     "tn_mesh_workspace_bytes": (_sz, [_i32, _i32, _i32]),
     "tn_tsdf_integrate": (C.c_int, [_vp] * 4 + [_i32, _i32, C.POINTER(tn_mesh_params), _vp, _vp]),
     "tn_mesh_extract": (C.c_int, [_vp, C.POINTER(tn_mesh_params)] + [_vp] * 5 + [_i64, _vp, _i64, _vp, _vp, _sz, _vp]),
+    "tn_mesh_components_workspace_bytes": (_sz, [_i64, _i64]),
+    "tn_mesh_components": (C.c_int, [_vp, _i64, _i64, _vp, _vp, _vp, _vp]),
+    "tn_mesh_filter_components": (C.c_int, [_vp, _i64, _i64, _vp, _vp, _vp, _i64, _i32, _vp, _i64, _vp, _i64, _vp, _vp, _sz, _vp]),
     "tn_render_workspace_bytes": (_sz, [C.POINTER(tn_render_config), _i64]),
     "tn_render_rays_fwd": (
         C.c_int,

@@ -1,5 +1,7 @@
 """Export of a trained scene as 3-D data: a thermal point cloud (positions, colours, degrees per point; optionally without
-statistical outliers and with normals, both from a k-nearest-neighbour search on the device), a thermal triangle mesh (TSDF fusion + surface nets, degrees per vertex) and their PLY files."""
+statistical outliers and with normals, both from a k-nearest-neighbour search on the device), a thermal triangle mesh (TSDF fusion + surface nets, degrees per vertex; optionally without its small connected components) and their PLY files."""
+from .components import (ComponentsInfo, MeshComponents, filter_components, mesh_components,  # noqa: F401
+                         mesh_components_workspace_bytes, remove_small_components)
 from .mesh import (MeshExporter, ThermalMesh, camera_pose, grid_dims, mesh_extract, mesh_params, mesh_scan_width,  # noqa: F401
                    mesh_tile, mesh_workspace_bytes, set_camera, tsdf_integrate, world_to_camera)
 from .neighbors import (Neighbors, estimate_normals, knn, knn_grid_resolution, knn_workspace_bytes, outlier_keep_mask,  # noqa: F401

@@ -238,6 +238,7 @@ class MeshExporter(PoseExporter):
         self.truncation = float(truncation)
         self.params = mesh_params(box[0], box[1], self.dims, truncation, min_accumulation, max_temperature, min_temperature, to_world)
         self.last_poses = 0  # poses fused by the last export
+        self.last_components = None  # the ComponentsInfo of the last export, None when it removed no components
 
     @torch.no_grad()
     def fuse(self, cameras, camera_indices: Optional[Sequence[int]] = None, apply_camera_optimizer: bool = True) -> Tensor:
@@ -277,9 +278,21 @@ class MeshExporter(PoseExporter):
                          triangles=triangles, workspace=workspace)
         return ThermalMesh(positions, colors, temperature, thermal_colors, triangles, self.temperature_bounds)
 
-    def export(self, cameras, camera_indices: Optional[Sequence[int]] = None, apply_camera_optimizer: bool = True) -> ThermalMesh:
+    def export(self, cameras, camera_indices: Optional[Sequence[int]] = None, apply_camera_optimizer: bool = True,
+               min_component_triangles: int = 0, largest_component: bool = False) -> ThermalMesh:
         """Fuse ``cameras`` (all, or ``camera_indices``) in that order and return the surface.  ``apply_camera_optimizer``: adjust
         camera k's rays with row k of the model's pose table — right for the TRAINING cameras (pass False for other views).
         Cameras are rendered as PINHOLE views: ``distortion_params`` is ignored, because the export renders the model — it does
-        not match photographs — and the fusion kernel projects a voxel through a pinhole."""
-        return self.extract(self.fuse(cameras, camera_indices, apply_camera_optimizer))
+        not match photographs — and the fusion kernel projects a voxel through a pinhole.
+        ``min_component_triangles`` > 0 drops the connected components (the islands floaters turn into) of fewer triangles,
+        ``largest_component`` all but the largest (``remove_small_components``; ``last_components`` then tells what went).  With
+        both off the mesh is the extraction's, untouched."""
+        if int(min_component_triangles) < 0:
+            raise ValueError("min_component_triangles must not be negative")
+        mesh = self.extract(self.fuse(cameras, camera_indices, apply_camera_optimizer))
+        self.last_components = None
+        if int(min_component_triangles) > 0 or largest_component:
+            from .components import remove_small_components
+
+            mesh, self.last_components = remove_small_components(mesh, int(min_component_triangles), bool(largest_component))
+        return mesh

@@ -11,6 +11,12 @@ unless ``--bounding-box-min/-max``): ``--resolution`` grid points along the long
 extracted by surface nets; a vertex carries the mean colour and temperature of the near-surface observations around it.
 Training cameras are rendered with their optimised poses.
 
+A floater in the trained scene becomes a small closed island of triangles beside the real surface.  ``--min-component-triangles N``
+drops every connected component (triangles that share a vertex are connected) of fewer than N triangles, ``--largest-component``
+all but the largest; the temperature of the vertices that stay is untouched:
+
+    python tools/export_mesh.py RUN_DIR DATASET --output mesh.ply --resolution 256 --min-component-triangles 200
+
 Positions are written in the dataset's original world frame; ``--scene-frame`` keeps the normalised frame the model was trained in.
 """
 from __future__ import annotations
@@ -41,6 +47,9 @@ def parse(argv=None) -> argparse.Namespace:
     ap.add_argument("--bounding-box-min", type=float, nargs=3, default=None, metavar=("X", "Y", "Z"))
     ap.add_argument("--bounding-box-max", type=float, nargs=3, default=None, metavar=("X", "Y", "Z"))
     ap.add_argument("--colors", choices=("rgb", "thermal"), default="rgb", help="what fills red / green / blue")
+    ap.add_argument("--min-component-triangles", type=int, default=0, metavar="N",
+                    help="drop connected components of fewer than N triangles (0: off)")
+    ap.add_argument("--largest-component", action="store_true", help="keep only the connected component with the most triangles")
     ap.add_argument("--scene-frame", action="store_true", help="write the normalised scene frame, not the dataset's world frame")
     ap.add_argument("--config-json", type=Path, default=None, help="model fields that override the run's config.json")
     ap.add_argument("--device", default="cuda")
@@ -49,6 +58,8 @@ def parse(argv=None) -> argparse.Namespace:
         ap.error("--bounding-box-min and --bounding-box-max go together")
     if len(args.resolution) not in (1, 3) or min(args.resolution) < 2:
         ap.error("--resolution takes one number or three, each at least 2")
+    if args.min_component_triangles < 0:
+        ap.error("--min-component-triangles must not be negative")
     return args
 
 
@@ -72,11 +83,16 @@ def main(argv=None) -> int:
     from thermo_nerf_amd.export import write_mesh_ply
 
     exporter, cameras, adjust = build_exporter(args)
-    mesh = exporter.export(cameras, apply_camera_optimizer=adjust)
+    mesh = exporter.export(cameras, apply_camera_optimizer=adjust, min_component_triangles=args.min_component_triangles,
+                           largest_component=args.largest_component)
     write_mesh_ply(args.output, mesh, colors=args.colors)
     nx, ny, nz = exporter.dims
     print(f"poses fused {exporter.last_poses} into {nx} x {ny} x {nz}, vertices {len(mesh)}, triangles {int(mesh.triangles.shape[0])} "
           f"-> {args.output}")
+    info = exporter.last_components
+    if info is not None:
+        print(f"components found {info.components}, largest {info.largest_triangles} triangles, removed vertices {info.vertices_removed}, "
+              f"triangles {info.triangles_removed}")
     if len(mesh):
         print(f"temperature min {float(mesh.temperature.min()):.3f} C, max {float(mesh.temperature.max()):.3f} C")
     else:

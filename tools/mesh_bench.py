@@ -12,7 +12,14 @@ One warm-up pass per route, then ``--passes`` timed passes per route, alternatin
 drift of a shared machine hits all alike; a pass is timed with the host clock around work that ends in a device synchronise.
 The report gives the median and the range per route.  A record, not a gate.
 
+``--components-out``: afterwards, on the mesh of the same run, the connected-components kernels (tn_mesh_components +
+tn_mesh_filter_components into preallocated outputs at their upper bounds, min_triangles = 2) beside one emitting tn_mesh_extract
+call, both by device events: 3 warm-up calls, then ``--repeats`` windows of ``--calls`` back-to-back calls each, median and range of
+the ms per call.  The same for ``--copies`` disjoint copies of the mesh in one index list (the 10^5 - 10^6 vertices of a scene
+with real surfaces; the bench model's initial weights give a small mesh).
+
     python tools/mesh_bench.py [--passes 5] [--poses 8] [--downscale 1] [--resolution 256] [--out profiles/micro/export_mesh.txt]
+                               [--components-out profiles/micro/mesh_components.txt]
 """
 from __future__ import annotations
 
@@ -37,6 +44,10 @@ def main() -> int:
     ap.add_argument("--samples", type=int, default=48)
     ap.add_argument("--resolution", type=int, default=256)
     ap.add_argument("--out", default=None, help="also write the report to this file")
+    ap.add_argument("--components-out", default=None, help="time the connected-components kernels too and write that report here")
+    ap.add_argument("--repeats", type=int, default=15, help="event windows per timed call")
+    ap.add_argument("--calls", type=int, default=20, help="back-to-back calls per event window")
+    ap.add_argument("--copies", type=int, default=40, help="disjoint copies of the mesh in the large components timing")
     args = ap.parse_args()
 
     import torch
@@ -100,7 +111,91 @@ def main() -> int:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         with open(args.out, "w") as f:
             f.write(report)
+    if args.components_out:
+        report = components_report(args, exporter, state["volume"], mesh, med["extract"])
+        print(report)
+        os.makedirs(os.path.dirname(os.path.abspath(args.components_out)), exist_ok=True)
+        with open(args.components_out, "w") as f:
+            f.write(report)
     return 0
+
+
+def event_ms(fn, repeats: int, calls: int):
+    """(median, min, max) ms per call of ``fn``: 3 warm-up calls, then ``repeats`` event windows of ``calls`` calls each"""
+    import torch
+
+    for _ in range(3):
+        fn()
+    torch.cuda.synchronize()
+    per_call = []
+    for _ in range(repeats):
+        start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        start.record()
+        for _ in range(calls):
+            fn()
+        end.record()
+        end.synchronize()
+        per_call.append(start.elapsed_time(end) / calls)
+    per_call.sort()
+    return per_call[len(per_call) // 2], per_call[0], per_call[-1]
+
+
+def components_report(args, exporter, volume, mesh, extract_pass_ms: float) -> str:
+    import torch
+
+    from thermo_nerf_amd import _hip, colormaps
+    from thermo_nerf_amd.export import mesh_extract, mesh_workspace_bytes
+    from thermo_nerf_amd.export.components import mesh_components_workspace_bytes
+
+    lib, dev = _hip.load(), mesh.triangles.device
+    v, t = len(mesh), int(mesh.triangles.shape[0])
+
+    # one emitting tn_mesh_extract call into the mesh's own buffers
+    counts = torch.zeros((2,), dtype=torch.int64, device=dev)
+    ws = torch.empty((mesh_workspace_bytes(exporter.dims),), dtype=torch.uint8, device=dev)
+    table = colormaps.get_table(exporter.thermal_color_map, dev)[1]
+
+    def extract_call():
+        mesh_extract(volume, exporter.params, counts=counts, positions=mesh.positions, colors=mesh.colors, temperature=mesh.temperature,
+                     thermal_colors=mesh.thermal_colors, thermal_table=table, triangles=mesh.triangles, workspace=ws)
+
+    def components_call_on(tri, nv):
+        nt = int(tri.shape[0])
+        labels = torch.empty((nv,), dtype=torch.int32, device=dev)
+        component_triangles = torch.empty((nv,), dtype=torch.int32, device=dev)
+        summary = torch.empty((3,), dtype=torch.int64, device=dev)
+        source = torch.empty((nv,), dtype=torch.int32, device=dev)
+        out = torch.empty((nt, 3), dtype=torch.int32, device=dev)
+        kept = torch.empty((2,), dtype=torch.int64, device=dev)
+        cws = torch.empty((mesh_components_workspace_bytes(nv, nt),), dtype=torch.uint8, device=dev)
+        stream = _hip.current_stream()
+
+        def call():  # the C entries directly: the two calls a caller with preallocated outputs makes
+            _hip.check(lib.tn_mesh_components(tri.data_ptr(), nt, nv, labels.data_ptr(), component_triangles.data_ptr(),
+                                              summary.data_ptr(), stream), "tn_mesh_components")
+            _hip.check(lib.tn_mesh_filter_components(tri.data_ptr(), nt, nv, labels.data_ptr(), component_triangles.data_ptr(),
+                                                     summary.data_ptr(), 2, 0, source.data_ptr(), nv, out.data_ptr(), nt,
+                                                     kept.data_ptr(), cws.data_ptr(), cws.numel(), stream), "tn_mesh_filter_components")
+
+        return call, summary, kept
+
+    nx, ny, nz = exporter.dims
+    lines = [f"connected components of the mesh of tools/mesh_bench.py ({nx} x {ny} x {nz} volume, {args.poses} poses, S = {args.samples}): "
+             f"tn_mesh_components + tn_mesh_filter_components (min_triangles 2, outputs at their upper bounds) beside one emitting "
+             f"tn_mesh_extract call; device events, 3 warm-up calls, {args.repeats} windows of {args.calls} back-to-back calls, ms per call",
+             "what                                        vertices   triangles  components  kept v / t          median ms   min .. max"]
+    e = event_ms(extract_call, args.repeats, args.calls)
+    lines.append(f"{'tn_mesh_extract (emitting call)':43s} {v:9d} {t:11d}  {'-':>10s}  {'-':19s} {e[0]:9.4f}   {e[1]:.4f} .. {e[2]:.4f}")
+    big = torch.cat([mesh.triangles + k * v for k in range(args.copies)]) if t else mesh.triangles
+    for name, tri, nv in (("components + filter, the mesh", mesh.triangles, v),
+                          (f"components + filter, {args.copies} disjoint copies", big, v * args.copies)):
+        call, summary, kept = components_call_on(tri, nv)
+        c = event_ms(call, args.repeats, args.calls)
+        found, (kv, kt) = int(summary[0]), kept.tolist()
+        lines.append(f"{name:43s} {nv:9d} {int(tri.shape[0]):11d}  {found:10d}  {f'{kv} / {kt}':19s} {c[0]:9.4f}   {c[1]:.4f} .. {c[2]:.4f}")
+    lines.append(f"(MeshExporter.extract of the same run — sizing call, host read, allocation, emitting call — by the host clock: "
+                 f"{extract_pass_ms:.3f} ms, median)")
+    return "\n".join(lines) + "\n"
 
 
 if __name__ == "__main__":
