@@ -460,6 +460,70 @@ int tn_mesh_filter_components(const int32_t *triangles, int64_t num_triangles, i
                               int32_t largest_only, int32_t *vertex_source, int64_t capacity_vertices, int32_t *triangles_out,
                               int64_t capacity_triangles, int64_t *counts, void *workspace, size_t workspace_bytes, void *stream);
 
+/* A stable sort of n (uint64 key, int32 value) pairs on the device: a least-significant-digit radix sort, 8 bits per pass.
+ *   The ORDERING BITS of a key are its low 8 * ceil(key_bits / 8) bits.  keys_out / values_out hold the input pairs in ascending
+ *   order of their ordering bits; pairs whose ordering bits are equal keep their input order (the sort is stable).  Higher key
+ *   bits travel with the key and do not order.  The output is therefore unique: with m = keys_in masked to the ordering bits and
+ *   o = numpy's argsort(m, kind="stable"), keys_out = keys_in[o] and values_out = values_in[o] — or o itself when values_in is
+ *   NULL, which stands for the values 0 .. n-1.
+ *   keys_in / values_in are only read and must not overlap the outputs or the workspace.  The result is in keys_out / values_out
+ *   for every pass count, odd or even: the ping-pong partner of the output buffers lives in the workspace.
+ * workspace: tn_sort_pairs_workspace_bytes(n) device bytes, 8-byte aligned (partner keys and values, 256 counts per tile of
+ * tn_sort_tile() keys); it depends on n only.  Three launches per pass on `stream` (per-tile digit histogram, a one-block scan of
+ * the 256 * tiles counts, scatter), no allocation, no host synchronisation; no block waits for another (no decoupled look-back, no
+ * grid barrier).  The histogram counts with integer LDS atomics; nothing in the output depends on the order of arrival.
+ * TN_ERR_UNSUPPORTED: key_bits < 1 or > 64; TN_ERR_SHAPE: n < 0 or n > 2^31 - 1; n == 0: TN_OK, nothing is launched or written;
+ * then TN_ERR_NULL: keys_in, keys_out, values_out or workspace is NULL; TN_ERR_SHAPE: a key pointer or the workspace not 8-byte
+ * aligned, a value pointer not 4-byte aligned; TN_ERR_WORKSPACE: workspace_bytes too small.  All are returned before any launch.
+ * tn_sort_pairs_workspace_bytes is 0 for n < 0 or n > 2^31 - 1. */
+int32_t tn_sort_tile(void);
+size_t tn_sort_pairs_workspace_bytes(int64_t n);
+int tn_sort_pairs(const uint64_t *keys_in, const int32_t *values_in, int64_t n, int key_bits, uint64_t *keys_out,
+                  int32_t *values_out, void *workspace, size_t workspace_bytes, void *stream);
+
+/* Voxel down-sampling of a point cloud (the voxel grid filter of open3d / CloudCompare, with a temperature): one output point per
+ * occupied voxel, every attribute the mean over the voxel's members, defined to the bit.
+ *   parameters   origin[3] floats, voxel_size a float > 0 and finite, dims[3] int32, each in [1, 2^21] (TN_ERR_UNSUPPORTED
+ *                otherwise); total = dims_x * dims_y * dims_z (at most 2^63).
+ *   coordinate   inv = 1.0 / (double)voxel_size;  u_a = ((double)p_a - (double)origin_a) * inv — fp64, one correctly rounded
+ *                operation per step.
+ *   member       point i is a MEMBER iff its three coordinates are finite and 0 <= u_a < (double)dims_a on every axis (a NaN
+ *                fails); then c_a = (int64)u_a (truncation).  Every other point is dropped.
+ *   key          (c_z * dims_y + c_y) * dims_x + c_x; a dropped point gets `total`, which sorts behind every voxel.  The keys are
+ *                sorted with the point indices by tn_sort_pairs over key_bits = bit_length(total).
+ *   voxel        the members with one key, in ascending point index — the order the stable sort leaves them in.  Voxels are
+ *                written in ascending key.
+ *   positions_out, temperature_out   per component the fp64 sum from 0 in that order, divided by (double)n (n = the voxel's
+ *                members), rounded once to fp32.
+ *   colors_out, thermal_colors_out (uint8)   per channel the exact integer sum S, then (2 S + n) / (2 n) in integer division
+ *                (round half up).  thermal_colors_out may be NULL, and must be if thermal_colors is.
+ *   source_out   the source of the voxel's first member (its lowest point index); may be NULL, and must be if source is.
+ *   voxel_count  int32 n per output point.
+ *   count[0] (device int64) is OVERWRITTEN with the number of occupied voxels — the FULL number; nothing is written at or beyond
+ *   `capacity` (0 with NULL outputs: the sizing call).
+ * positions [num_points, 3] floats, colors / thermal_colors [num_points, 3] bytes, temperature [num_points] floats, source
+ * [num_points] int64; the outputs likewise over `capacity` rows.  workspace: tn_voxel_downsample_workspace_bytes(num_points) device
+ * bytes, 8-byte aligned.  Launches on `stream`: keys, tn_sort_pairs, then the heads of the runs compacted in order (count, one-block
+ * scan, emit), then one thread per voxel that walks its run; no atomics, no allocation, no host synchronisation, no block waits
+ * for another.  The walk is sequential per voxel (the sums are ordered by definition): a voxel of 10^5 members is 10^5 steps of
+ * one thread.
+ * TN_ERR_NULL: params or count is NULL; positions, colors, temperature or the workspace with num_points > 0; positions_out,
+ * colors_out, temperature_out or voxel_count with capacity > 0; thermal_colors_out without thermal_colors, source_out without
+ * source (with num_points > 0); TN_ERR_SHAPE: num_points < 0 or > 2^31 - 1, capacity < 0, a float / int32 pointer not 4-byte aligned, source /
+ * source_out / count / workspace not 8-byte aligned; TN_ERR_WORKSPACE: workspace_bytes too small.  All are returned before any
+ * launch.  num_points == 0: count[0] is zeroed by a memset, nothing is launched.  tn_voxel_downsample_workspace_bytes is 0 for
+ * num_points < 0 or > 2^31 - 1. */
+typedef struct tn_voxel_params {
+    float origin[3];
+    float voxel_size;
+    int32_t dims[3];
+} tn_voxel_params;
+size_t tn_voxel_downsample_workspace_bytes(int64_t num_points);
+int tn_voxel_downsample(const float *positions, const uint8_t *colors, const float *temperature, const uint8_t *thermal_colors,
+                        const int64_t *source, int64_t num_points, const tn_voxel_params *params, float *positions_out,
+                        uint8_t *colors_out, float *temperature_out, uint8_t *thermal_colors_out, int64_t *source_out,
+                        int32_t *voxel_count, int64_t capacity, int64_t *count, void *workspace, size_t workspace_bytes, void *stream);
+
 /* ------------------------------------------------------------------------------------------------------
  * Fused forward: Model.forward (collider) + ThermalNerfModel.get_outputs
  * [REF thermal_nerf_model.py:210-275]

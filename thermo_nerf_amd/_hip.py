@@ -82,6 +82,10 @@ class tn_pointcloud_params(C.Structure):
                 ("to_world", C.c_float * 12)]
 
 
+class tn_voxel_params(C.Structure):
+    _fields_ = [("origin", C.c_float * 3), ("voxel_size", C.c_float), ("dims", C.c_int32 * 3)]
+
+
 class tn_mesh_params(C.Structure):
     _fields_ = [("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("w2c", C.c_float * 12),
                 ("truncation", C.c_float), ("inv_truncation", C.c_float), ("min_accumulation", C.c_float), ("lo", C.c_float * 3),
@@ -230,6 +234,11 @@ SIGNATURES = {
     "tn_knn_workspace_bytes": (_sz, [_i64, _i32]),
     "tn_knn": (C.c_int, [_vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _sz, _vp]),
     "tn_pointcloud_normals": (C.c_int, [_vp, _vp, _i64, _i32, _vp, _vp, _vp]),
+    "tn_sort_tile": (_i32, []),
+    "tn_sort_pairs_workspace_bytes": (_sz, [_i64]),
+    "tn_sort_pairs": (C.c_int, [_vp, _vp, _i64, C.c_int, _vp, _vp, _vp, _sz, _vp]),
+    "tn_voxel_downsample_workspace_bytes": (_sz, [_i64]),
+    "tn_voxel_downsample": (C.c_int, [_vp] * 5 + [_i64, C.POINTER(tn_voxel_params)] + [_vp] * 6 + [_i64, _vp, _vp, _sz, _vp]),
     "tn_mesh_tile": (_i32, []),
     "tn_mesh_scan_width": (_i32, []),
     "tn_mesh_workspace_bytes": (_sz, [_i32, _i32, _i32]),

@@ -17,11 +17,15 @@ and deterministically (point floor(j M / N) for j < N).
 ``--remove-outliers`` drops the floaters first (statistical outlier removal over ``--outlier-neighbors`` neighbours: a point goes
 when its mean neighbour distance is ``--outlier-std-ratio`` standard deviations above the cloud's mean); ``--normals`` gives every
 written point a normal (nx ny nz in the file) from its ``--normal-neighbors`` nearest neighbours, turned towards the camera the
-point was seen from.  Order: export, outlier removal, thinning, normals — the normals are those of the cloud that is written.
+point was seen from.  ``--voxel-size S`` replaces the points of every occupied voxel of edge S — in the units of the frame that is
+written: the world frame, or the scene frame with ``--scene-frame`` — by ONE point with their mean position, colours and
+temperature: a wall seen by forty cameras is in the cloud once, at the mean of the forty measurements.  Order: export, outlier
+removal, voxel down-sampling, thinning, normals — the normals are those of the cloud that is written.
 """
 from __future__ import annotations
 
 import argparse
+import math
 import os
 import sys
 from pathlib import Path
@@ -66,6 +70,8 @@ def parse(argv=None) -> argparse.Namespace:
     ap.add_argument("--remove-outliers", action="store_true", help="drop statistical outliers before thinning")
     ap.add_argument("--outlier-neighbors", type=int, default=20, help="neighbours of the outlier statistic, the point included")
     ap.add_argument("--outlier-std-ratio", type=float, default=10.0, help="standard deviations above the mean that make an outlier")
+    ap.add_argument("--voxel-size", type=float, default=None, metavar="S",
+                    help="one averaged point per occupied voxel of edge S, in the units of the frame that is written")
     ap.add_argument("--normals", action="store_true", help="estimate a normal per written point (nx ny nz in the file)")
     ap.add_argument("--normal-neighbors", type=int, default=30, help="nearest neighbours a normal is fitted to")
     ap.add_argument("--device", default="cuda")
@@ -80,6 +86,8 @@ def parse(argv=None) -> argparse.Namespace:
         ap.error("--bounding-box-min and --bounding-box-max go together")
     if args.no_bounding_box and args.bounding_box_min is not None:
         ap.error("--no-bounding-box contradicts --bounding-box-min/-max")
+    if args.voxel_size is not None and not (args.voxel_size > 0.0 and math.isfinite(args.voxel_size)):
+        ap.error("--voxel-size must be positive and finite")
     if args.num_points < 0:
         ap.error("--num-points must not be negative")
     return args
@@ -117,6 +125,12 @@ def main(argv=None) -> int:
 
         cloud, _ = remove_statistical_outliers(cloud, args.outlier_neighbors, args.outlier_std_ratio)
         removed = f", outliers removed {kept - len(cloud)}"
+    if args.voxel_size is not None:
+        from thermo_nerf_amd.export import voxel_downsample
+
+        before = len(cloud)
+        cloud, _ = voxel_downsample(cloud, args.voxel_size)
+        removed += f", voxels {len(cloud)} of {before}"
     cloud = subsample(cloud, args.num_points)
     if args.normals:
         from thermo_nerf_amd.export import estimate_normals
