@@ -460,6 +460,63 @@ int tn_mesh_filter_components(const int32_t *triangles, int64_t num_triangles, i
                               int32_t largest_only, int32_t *vertex_source, int64_t capacity_vertices, int32_t *triangles_out,
                               int64_t capacity_triangles, int64_t *counts, void *workspace, size_t workspace_bytes, void *stream);
 
+/* Vertex normals and Taubin smoothing of an indexed triangle list, on a device incidence index: per vertex, the list of its incident
+ * triangle corners in a fixed order.  A vertex's sum is then one thread's loop over its own list, so every float below is defined to
+ * the bit and the same on every run; there are no float atomics.  positions [V, 3] device floats, triangles [T, 3] device int32,
+ * V = num_vertices, T = num_triangles; CORNER c = 3 t + j is index j of triangle t.  add / sub / mul / div / sqrt below are single
+ * correctly rounded fp32 operations, nothing is contracted.
+ * tn_mesh_incidence: offsets (int32 [V + 1]) and corners (int32 [3 T]).
+ *   A triangle is VALID as in tn_mesh_components: all three indices in [0, V).  A valid triangle with a repeated index is listed
+ *   once per corner.
+ *   The KEY of corner c is the vertex index it names if its triangle is valid, else V.
+ *   corners: the corner numbers 0 .. 3T-1 in ascending key order, equal keys in ascending corner order — tn_sort_pairs with
+ *   values_in = NULL over max(1, bit_length(V)) key bits, i.e. numpy's argsort(keys, kind="stable").  The rows at and beyond
+ *   offsets[V] therefore hold the corners of the invalid triangles in ascending order: every row is defined.
+ *   offsets[v], v = 0 .. V: the number of keys < v (the lower bound in the sorted keys; one thread per v, a binary search).  The
+ *   list of vertex v is corners[offsets[v] .. offsets[v + 1]).
+ *   V == 0 or T == 0: offsets (V + 1 entries) is zeroed by a memset, nothing is launched, corners is untouched.
+ *   workspace: tn_mesh_incidence_workspace_bytes(V, T) device bytes, 8-byte aligned (the keys, the sorted keys, the sort's own
+ *   workspace); 0 for counts out of range.  Launches on `stream`: keys, tn_sort_pairs, offsets.
+ * tn_mesh_vertex_normals: normals (float [V, 3]), one thread per vertex.
+ *   face vector of t: e1 = sub(p1, p0), e2 = sub(p2, p0) per component (p0 p1 p2 = the positions of its indices 0 1 2), then
+ *   f = (sub(mul(e1y, e2z), mul(e1z, e2y)), sub(mul(e1z, e2x), mul(e1x, e2z)), sub(mul(e1x, e2y), mul(e1y, e2x))).  Its length is
+ *   twice the area (area weighting); it points outward, because the extraction winds its triangles that way; it is exactly 0 for
+ *   a repeated index.
+ *   vertex sum: s = 0; for the corners of v's list in list order, s_c = add(s_c, f_c) with f of the corner's triangle.
+ *   normal: len = sqrt(add(add(mul(sx, sx), mul(sy, sy)), mul(sz, sz))); if len > 0 and len < +inf, n_c = div(s_c, len), otherwise
+ *   (0, 0, 0) — which also covers a NaN and a vertex in no valid triangle.
+ * tn_mesh_smooth: positions_out (float [V, 3]) = positions_in after `iterations` >= 0 iterations; scratch: float [V, 3].
+ *   A PASS with factor k, src -> dst (Jacobi: src is only read, dst only written, one thread per vertex): s = 0, n = 0; for the
+ *   corners of v's list in list order, corner (t, j): q = src[t[(j + 1) % 3]], r = src[t[(j + 2) % 3]], s_c = add(add(s_c, q_c),
+ *   r_c), n += 2.  If n == 0, dst[v] = src[v].  Otherwise m_c = div(s_c, float(n)) and dst_c = add(p_c, mul(k, sub(m_c, p_c)))
+ *   with p = src[v].
+ *   Why corner weights: in the interior of a manifold mesh every edge neighbour is met in exactly two triangles, so this is the
+ *   uniform umbrella operator; on an open border the two border neighbours weigh half.  No per-vertex de-duplication is needed,
+ *   and every value is defined by the list order.
+ *   An ITERATION is a pass with lambda, then a pass with mu (Taubin's non-shrinking filter: lambda > 0, mu < -lambda).  Any finite
+ *   pair is accepted.  The passes alternate in -> scratch -> out -> scratch -> out ..., so the result is in positions_out for every
+ *   iteration count; iterations == 0 is a device copy.  positions_out == positions_in is allowed; otherwise the two must not
+ *   overlap, and scratch must overlap neither.  Only positions move: a vertex keeps the colour and temperature it was born with.
+ * offsets / corners of the two per-vertex entries are tn_mesh_incidence's of the SAME triangles and V.  The kernels check what they
+ * dereference (a list is clipped to [0, 3T], a corner outside it or of an invalid triangle is skipped), so a foreign index gives
+ * other numbers, never an access outside the arrays.
+ * All launches are plain, 256-thread blocks on `stream`; no allocation, no host synchronisation, no float atomics, and no block
+ * ever waits for another (no look-back, no grid barrier, no cooperative launch).  The loop of a vertex is sequential because the
+ * sums are ordered by definition: a star of 10^5 corners is 10^5 steps of one thread (a surface-nets vertex has 4 - 8).
+ * TN_ERR_NULL: a required pointer is NULL (offsets always for tn_mesh_incidence, and with V > 0 and T > 0 triangles, corners, the
+ * workspace; for the other two, with V > 0: positions, offsets, the output, and with T > 0 triangles and corners; scratch with
+ * V > 0 and iterations > 0); TN_ERR_SHAPE: V < 0 or > 2^31 - 1, T < 0 or 3T > 2^31 - 1, iterations < 0, a pointer not 4-byte
+ * aligned, the workspace not 8-byte aligned, buffers of tn_mesh_smooth that overlap; TN_ERR_UNSUPPORTED: lambda or mu not finite;
+ * TN_ERR_WORKSPACE: workspace_bytes too small.  All are returned before any launch.  V == 0: TN_OK, nothing is launched. */
+size_t tn_mesh_incidence_workspace_bytes(int64_t num_vertices, int64_t num_triangles);
+int tn_mesh_incidence(const int32_t *triangles, int64_t num_triangles, int64_t num_vertices, int32_t *offsets, int32_t *corners,
+                      void *workspace, size_t workspace_bytes, void *stream);
+int tn_mesh_vertex_normals(const float *positions, const int32_t *triangles, int64_t num_triangles, int64_t num_vertices,
+                           const int32_t *offsets, const int32_t *corners, float *normals, void *stream);
+int tn_mesh_smooth(const float *positions_in, const int32_t *triangles, int64_t num_triangles, int64_t num_vertices,
+                   const int32_t *offsets, const int32_t *corners, int32_t iterations, float lambda, float mu, float *positions_out,
+                   float *scratch, void *stream);
+
 /* A stable sort of n (uint64 key, int32 value) pairs on the device: a least-significant-digit radix sort, 8 bits per pass.
  *   The ORDERING BITS of a key are its low 8 * ceil(key_bits / 8) bits.  keys_out / values_out hold the input pairs in ascending
  *   order of their ordering bits; pairs whose ordering bits are equal keep their input order (the sort is stable).  Higher key

@@ -16,6 +16,10 @@ namespace tn {
 __device__ __forceinline__ float mul_rn(float a, float b) { return __fmul_rn(a, b); }
 __device__ __forceinline__ float add_rn(float a, float b) { return __fadd_rn(a, b); }
 __device__ __forceinline__ float sub_rn(float a, float b) { return __fsub_rn(a, b); }
+// correctly rounded fp32 quotient and root through fp64 (53 bits >= 2 * 24 + 2: the second rounding changes nothing); the mesh
+// kernels' division and square root (tn_mesh.hip, tn_mesh_smooth.hip)
+__device__ __forceinline__ float div_rn(float a, float b) { return (float)((double)a / (double)b); }
+__device__ __forceinline__ float sqrt_rn(float a) { return (float)sqrt((double)a); }
 
 // one row m[0..3] of a 3 x 4 affine map applied to p, in this association only: ((m0 p0 + m1 p1) + m2 p2) + m3
 __device__ __forceinline__ float affine_row(const float *m, const float *p) {

@@ -31,10 +31,6 @@ namespace {
 
 constexpr int kTile = 256;  // cells / grid points per tile = threads per block of every kernel but the scan
 
-// correctly rounded fp32 quotient and root through fp64 (see the head of the file)
-__device__ __forceinline__ float div_rn(float a, float b) { return (float)((double)a / (double)b); }
-__device__ __forceinline__ float sqrt_rn(float a) { return (float)sqrt((double)a); }
-
 struct Dims {
     int nx, ny, nz;
     long long points;  // nx * ny * nz <= 2^31 - 1

@@ -132,5 +132,6 @@ def remove_small_components(mesh: ThermalMesh, min_triangles: int = 1, largest_o
         out = ThermalMesh(mesh.positions.index_select(0, source), mesh.colors.index_select(0, source),
                           mesh.temperature.index_select(0, source),
                           None if mesh.thermal_colors is None else mesh.thermal_colors.index_select(0, source),
-                          triangles[:kept_t], mesh.temperature_bounds)
+                          triangles[:kept_t], mesh.temperature_bounds,
+                          None if mesh.normals is None else mesh.normals.index_select(0, source))
     return out, ComponentsInfo(components, largest, v - kept_v, t - kept_t)

@@ -157,7 +157,8 @@ def mesh_extract(volume: Tensor, params, *, counts: Tensor, positions: Optional[
 class ThermalMesh:
     """V vertices and T triangles on the device: positions [V,3] float32, colors [V,3] uint8 (rendered RGB), temperature [V] float32
     in degrees Celsius, thermal_colors [V,3] uint8 (the colour-mapped normalised temperature), triangles [T,3] int32 (vertex
-    indices, normals from inside to outside).  ``temperature_bounds``: the (min, max) degrees the normalised output was scaled with."""
+    indices, normals from inside to outside).  ``temperature_bounds``: the (min, max) degrees the normalised output was scaled with.
+    ``normals``: [V,3] float32 unit vertex normals (``vertex_normals``), None unless asked for."""
 
     positions: Tensor
     colors: Tensor
@@ -165,6 +166,7 @@ class ThermalMesh:
     thermal_colors: Optional[Tensor] = None
     triangles: Optional[Tensor] = None
     temperature_bounds: Optional[Tuple[float, float]] = None
+    normals: Optional[Tensor] = None
 
     def __len__(self) -> int:
         return int(self.positions.shape[0])
@@ -279,20 +281,30 @@ class MeshExporter(PoseExporter):
         return ThermalMesh(positions, colors, temperature, thermal_colors, triangles, self.temperature_bounds)
 
     def export(self, cameras, camera_indices: Optional[Sequence[int]] = None, apply_camera_optimizer: bool = True,
-               min_component_triangles: int = 0, largest_component: bool = False) -> ThermalMesh:
+               min_component_triangles: int = 0, largest_component: bool = False, smooth_iterations: int = 0,
+               smooth_lambda: float = 0.5, smooth_mu: float = -0.53, normals: bool = False) -> ThermalMesh:
         """Fuse ``cameras`` (all, or ``camera_indices``) in that order and return the surface.  ``apply_camera_optimizer``: adjust
         camera k's rays with row k of the model's pose table — right for the TRAINING cameras (pass False for other views).
         Cameras are rendered as PINHOLE views: ``distortion_params`` is ignored, because the export renders the model — it does
         not match photographs — and the fusion kernel projects a voxel through a pinhole.
         ``min_component_triangles`` > 0 drops the connected components (the islands floaters turn into) of fewer triangles,
         ``largest_component`` all but the largest (``remove_small_components``; ``last_components`` then tells what went).  With
-        both off the mesh is the extraction's, untouched."""
+        both off the mesh is the extraction's, untouched.
+        ``smooth_iterations`` > 0 then relaxes the positions by that many Taubin iterations with the factors ``smooth_lambda`` /
+        ``smooth_mu`` (``smooth_mesh``; colours and temperature do not move), and ``normals`` adds the area-weighted vertex normals
+        of the FINAL positions and triangles.  With both off none of that code is called."""
         if int(min_component_triangles) < 0:
             raise ValueError("min_component_triangles must not be negative")
+        if int(smooth_iterations) < 0:
+            raise ValueError("smooth_iterations must not be negative")
         mesh = self.extract(self.fuse(cameras, camera_indices, apply_camera_optimizer))
         self.last_components = None
         if int(min_component_triangles) > 0 or largest_component:
             from .components import remove_small_components
 
             mesh, self.last_components = remove_small_components(mesh, int(min_component_triangles), bool(largest_component))
+        if int(smooth_iterations) > 0 or normals:
+            from .smooth import smooth_mesh
+
+            mesh = smooth_mesh(mesh, int(smooth_iterations), smooth_lambda, smooth_mu, normals=bool(normals))
         return mesh

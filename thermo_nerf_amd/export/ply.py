@@ -22,6 +22,7 @@ No time stamp, no host name: the same cloud gives the same bytes.
 
 A cloud that carries normals (``estimate_normals``) is written with ``property float nx`` / ``ny`` / ``nz`` between ``z`` and
 ``red``: 31 bytes per vertex, the layout cloud viewers and Poisson reconstruction expect.  Without normals the file is the one above.
+A mesh (below) with ``normals`` set (``vertex_normals``) gets the same three properties in the same place.
 """
 from __future__ import annotations
 
@@ -73,6 +74,26 @@ def _vertex_array(obj, colors: str, dtype, no_thermal: str, disagree: str) -> np
     return vertex
 
 
+def _fill_normals(vertex: np.ndarray, normals) -> None:
+    nrm = _host(normals)
+    if nrm.shape != (vertex.shape[0], 3):
+        raise ValueError("normals must be [M,3]")
+    vertex["nx"], vertex["ny"], vertex["nz"] = nrm[:, 0], nrm[:, 1], nrm[:, 2]
+
+
+def _vertex_dtype(properties, face_lines, path, what: str):
+    """the record of a file's vertex properties: the 19-byte layout, or the 31-byte one with normals"""
+    if properties == _PROPERTIES + face_lines:
+        return VERTEX_DTYPE
+    if properties == _NORMAL_PROPERTIES + face_lines:
+        return NORMAL_VERTEX_DTYPE
+    raise ValueError(f"{path}: {what}")
+
+
+def _read_normals(vertex: np.ndarray) -> np.ndarray:
+    return np.stack([vertex["nx"], vertex["ny"], vertex["nz"]], axis=1) if vertex.shape[0] else np.zeros((0, 3), np.float32)
+
+
 def _write(path, head: str, *arrays: np.ndarray) -> Path:
     path = Path(path)
     path.parent.mkdir(parents=True, exist_ok=True)
@@ -110,13 +131,9 @@ def write_ply(path, cloud, colors: str = "rgb") -> Path:
     vertex = _vertex_array(cloud, colors, VERTEX_DTYPE if normals is None else NORMAL_VERTEX_DTYPE,
                            "the cloud holds no thermal colours (exported without a colour table)",
                            "positions [M,3], colours [M,3] and temperature [M] must agree")
-    m = vertex.shape[0]
     if normals is not None:
-        nrm = _host(normals)
-        if nrm.shape != (m, 3):
-            raise ValueError("normals must be [M,3]")
-        vertex["nx"], vertex["ny"], vertex["nz"] = nrm[:, 0], nrm[:, 1], nrm[:, 2]
-    return _write(path, header(m, getattr(cloud, "temperature_bounds", None), normals is not None), vertex)
+        _fill_normals(vertex, normals)
+    return _write(path, header(vertex.shape[0], getattr(cloud, "temperature_bounds", None), normals is not None), vertex)
 
 
 def read_ply(path) -> Dict:
@@ -128,63 +145,69 @@ def read_ply(path) -> Dict:
     if len(counts) != 1 or not counts[0].startswith("element vertex "):
         raise ValueError(f"{path}: one vertex element expected")
     properties = tuple(ln for ln in lines if ln.startswith("property "))
-    if properties not in (_PROPERTIES, _NORMAL_PROPERTIES):
-        raise ValueError(f"{path}: vertex properties differ from x y z [nx ny nz] red green blue temperature")
-    dtype = VERTEX_DTYPE if properties == _PROPERTIES else NORMAL_VERTEX_DTYPE
+    dtype = _vertex_dtype(properties, (), path, "vertex properties differ from x y z [nx ny nz] red green blue temperature")
     m = int(counts[0].split()[2])
     if len(blob) - body != m * dtype.itemsize:
         raise ValueError(f"{path}: {len(blob) - body} body bytes for {m} vertices of {dtype.itemsize} bytes")
     vertex = np.frombuffer(blob, dtype=dtype, count=m, offset=body)
     out = _vertex_fields(vertex, comments)
     if dtype is NORMAL_VERTEX_DTYPE:
-        out["normals"] = np.stack([vertex["nx"], vertex["ny"], vertex["nz"]], axis=1) if m else np.zeros((0, 3), np.float32)
+        out["normals"] = _read_normals(vertex)
     return out
 
 
 # ---- triangle meshes ---------------------------------------------------------------------------------------------------------------
 # The cloud's header up to its last vertex property, then ``element face T`` / ``property list uchar int vertex_indices``: 19 bytes per
 # vertex, 13 per face (the count byte 3 and three little-endian int32).  The same determinism: the same mesh gives the same bytes.
+# A mesh that carries normals (``vertex_normals``) is written like a cloud that does: nx ny nz between z and red, 31 bytes per vertex.
 FACE_DTYPE = np.dtype([("n", "u1"), ("v", "<i4", (3,))])
 assert FACE_DTYPE.itemsize == 13
 
 _FACE_LINES = ("property list uchar int vertex_indices",)
 
 
-def mesh_header(num_vertices: int, num_triangles: int, temperature_bounds=None) -> str:
-    lines = header(num_vertices, temperature_bounds).split("\n")[:-2]  # without end_header
+def mesh_header(num_vertices: int, num_triangles: int, temperature_bounds=None, normals: bool = False) -> str:
+    lines = header(num_vertices, temperature_bounds, normals).split("\n")[:-2]  # without end_header
     return "\n".join(lines + [f"element face {int(num_triangles)}", *_FACE_LINES, "end_header"]) + "\n"
 
 
 def write_mesh_ply(path, mesh, colors: str = "rgb") -> Path:
     """Write ``mesh`` (a ThermalMesh, on the device or the host) to ``path``; ``colors`` as in ``write_ply``.  V = 0 or T = 0 is a
-    valid file.  One device -> host copy per array."""
+    valid file.  ``mesh.normals``, where set, are written as nx ny nz behind z.  One device -> host copy per array."""
     disagree = "positions [V,3], colours [V,3], temperature [V] and triangles [T,3] must agree"
-    vertex = _vertex_array(mesh, colors, VERTEX_DTYPE, "the mesh holds no thermal colours (extracted without a colour table)", disagree)
+    normals = getattr(mesh, "normals", None)
+    vertex = _vertex_array(mesh, colors, VERTEX_DTYPE if normals is None else NORMAL_VERTEX_DTYPE,
+                           "the mesh holds no thermal colours (extracted without a colour table)", disagree)
     tri = _host(mesh.triangles)
     m, t = vertex.shape[0], tri.shape[0]
     if tri.shape != (t, 3):
         raise ValueError(disagree)
+    if normals is not None:
+        _fill_normals(vertex, normals)
     if t and (tri.min() < 0 or tri.max() >= m):
         raise ValueError("a triangle names a vertex outside [0, V)")
     face = np.empty(t, dtype=FACE_DTYPE)
     face["n"], face["v"] = 3, tri
-    return _write(path, mesh_header(m, t, getattr(mesh, "temperature_bounds", None)), vertex, face)
+    return _write(path, mesh_header(m, t, getattr(mesh, "temperature_bounds", None), normals is not None), vertex, face)
 
 
 def read_mesh_ply(path) -> Dict:
     """The arrays of a file ``write_mesh_ply`` wrote: ``read_ply``'s ``positions`` / ``colors`` / ``temperature`` / ``comments`` and
-    ``triangles`` int32 [T,3]."""
+    ``triangles`` int32 [T,3], and ``normals`` float32 [V,3] when the file carries them (the 31-byte vertex)."""
     blob, body, lines, comments = _read_header(path)
     counts = [ln.split() for ln in lines if ln.startswith("element ")]
     if [c[1] for c in counts] != ["vertex", "face"]:
         raise ValueError(f"{path}: a vertex element and a face element expected")
-    if tuple(ln for ln in lines if ln.startswith("property ")) != _PROPERTIES + _FACE_LINES:
-        raise ValueError(f"{path}: properties differ from x y z red green blue temperature / vertex_indices")
+    dtype = _vertex_dtype(tuple(ln for ln in lines if ln.startswith("property ")), _FACE_LINES, path,
+                          "properties differ from x y z [nx ny nz] red green blue temperature / vertex_indices")
     m, t = int(counts[0][2]), int(counts[1][2])
-    if len(blob) - body != m * VERTEX_DTYPE.itemsize + t * FACE_DTYPE.itemsize:
+    if len(blob) - body != m * dtype.itemsize + t * FACE_DTYPE.itemsize:
         raise ValueError(f"{path}: {len(blob) - body} body bytes for {m} vertices and {t} faces")
-    vertex = np.frombuffer(blob, dtype=VERTEX_DTYPE, count=m, offset=body)
-    face = np.frombuffer(blob, dtype=FACE_DTYPE, count=t, offset=body + m * VERTEX_DTYPE.itemsize)
+    vertex = np.frombuffer(blob, dtype=dtype, count=m, offset=body)
+    face = np.frombuffer(blob, dtype=FACE_DTYPE, count=t, offset=body + m * dtype.itemsize)
     if t and not (face["n"] == 3).all():
         raise ValueError(f"{path}: only triangles are read")
-    return {**_vertex_fields(vertex, comments), "triangles": face["v"].astype(np.int32).reshape(t, 3)}
+    out = {**_vertex_fields(vertex, comments), "triangles": face["v"].astype(np.int32).reshape(t, 3)}
+    if dtype is NORMAL_VERTEX_DTYPE:
+        out["normals"] = _read_normals(vertex)
+    return out

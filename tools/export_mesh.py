@@ -17,11 +17,19 @@ all but the largest; the temperature of the vertices that stay is untouched:
 
     python tools/export_mesh.py RUN_DIR DATASET --output mesh.ply --resolution 256 --min-component-triangles 200
 
+Surface nets place a vertex at the mean of its cell's edge crossings, so the facets of the voxel grid show in a shaded view.
+``--smooth-iterations N`` relaxes the positions with N Taubin iterations (a pass with ``--smooth-lambda``, a pass with
+``--smooth-mu``; the pair does not shrink the surface as plain Laplacian smoothing does), after the components are removed;
+``--normals`` writes the area-weighted vertex normals of the final surface as ``nx ny nz``.  Colours and temperature do not move:
+
+    python tools/export_mesh.py RUN_DIR DATASET --output mesh.ply --resolution 256 --smooth-iterations 10 --normals
+
 Positions are written in the dataset's original world frame; ``--scene-frame`` keeps the normalised frame the model was trained in.
 """
 from __future__ import annotations
 
 import argparse
+import math
 import os
 import sys
 from pathlib import Path
@@ -50,6 +58,10 @@ def parse(argv=None) -> argparse.Namespace:
     ap.add_argument("--min-component-triangles", type=int, default=0, metavar="N",
                     help="drop connected components of fewer than N triangles (0: off)")
     ap.add_argument("--largest-component", action="store_true", help="keep only the connected component with the most triangles")
+    ap.add_argument("--smooth-iterations", type=int, default=0, metavar="N", help="Taubin smoothing iterations (0: off)")
+    ap.add_argument("--smooth-lambda", type=float, default=0.5, help="the factor of an iteration's first pass (> 0)")
+    ap.add_argument("--smooth-mu", type=float, default=-0.53, help="the factor of an iteration's second pass (< -lambda)")
+    ap.add_argument("--normals", action="store_true", help="write the vertex normals of the final surface as nx ny nz")
     ap.add_argument("--scene-frame", action="store_true", help="write the normalised scene frame, not the dataset's world frame")
     ap.add_argument("--config-json", type=Path, default=None, help="model fields that override the run's config.json")
     ap.add_argument("--device", default="cuda")
@@ -60,6 +72,11 @@ def parse(argv=None) -> argparse.Namespace:
         ap.error("--resolution takes one number or three, each at least 2")
     if args.min_component_triangles < 0:
         ap.error("--min-component-triangles must not be negative")
+    if args.smooth_iterations < 0:
+        ap.error("--smooth-iterations must not be negative")
+    if not (args.smooth_lambda > 0.0 and args.smooth_mu < -args.smooth_lambda and math.isfinite(args.smooth_lambda)
+            and math.isfinite(args.smooth_mu)):
+        ap.error("--smooth-lambda must be positive and --smooth-mu below its negative, both finite")
     return args
 
 
@@ -84,11 +101,12 @@ def main(argv=None) -> int:
 
     exporter, cameras, adjust = build_exporter(args)
     mesh = exporter.export(cameras, apply_camera_optimizer=adjust, min_component_triangles=args.min_component_triangles,
-                           largest_component=args.largest_component)
+                           largest_component=args.largest_component, smooth_iterations=args.smooth_iterations,
+                           smooth_lambda=args.smooth_lambda, smooth_mu=args.smooth_mu, normals=args.normals)
     write_mesh_ply(args.output, mesh, colors=args.colors)
     nx, ny, nz = exporter.dims
-    print(f"poses fused {exporter.last_poses} into {nx} x {ny} x {nz}, vertices {len(mesh)}, triangles {int(mesh.triangles.shape[0])} "
-          f"-> {args.output}")
+    print(f"poses fused {exporter.last_poses} into {nx} x {ny} x {nz}, vertices {len(mesh)}, triangles {int(mesh.triangles.shape[0])}, "
+          f"smoothing iterations {args.smooth_iterations}, normals {'yes' if mesh.normals is not None else 'no'} -> {args.output}")
     info = exporter.last_components
     if info is not None:
         print(f"components found {info.components}, largest {info.largest_triangles} triangles, removed vertices {info.vertices_removed}, "

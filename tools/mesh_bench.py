@@ -18,8 +18,11 @@ call, both by device events: 3 warm-up calls, then ``--repeats`` windows of ``--
 the ms per call.  The same for ``--copies`` disjoint copies of the mesh in one index list (the 10^5 - 10^6 vertices of a scene
 with real surfaces; the bench model's initial weights give a small mesh).
 
+``--smooth-out``: the same protocol for the incidence index (tn_mesh_incidence), the vertex normals (tn_mesh_vertex_normals) and 10
+Taubin iterations (tn_mesh_smooth), each timed on its own into preallocated outputs, on the mesh and on its ``--copies`` copies.
+
     python tools/mesh_bench.py [--passes 5] [--poses 8] [--downscale 1] [--resolution 256] [--out profiles/micro/export_mesh.txt]
-                               [--components-out profiles/micro/mesh_components.txt]
+                               [--components-out profiles/micro/mesh_components.txt] [--smooth-out profiles/micro/mesh_smooth.txt]
 """
 from __future__ import annotations
 
@@ -45,6 +48,7 @@ def main() -> int:
     ap.add_argument("--resolution", type=int, default=256)
     ap.add_argument("--out", default=None, help="also write the report to this file")
     ap.add_argument("--components-out", default=None, help="time the connected-components kernels too and write that report here")
+    ap.add_argument("--smooth-out", default=None, help="time the incidence index, the normals and 10 smoothing iterations too and write that report here")
     ap.add_argument("--repeats", type=int, default=15, help="event windows per timed call")
     ap.add_argument("--calls", type=int, default=20, help="back-to-back calls per event window")
     ap.add_argument("--copies", type=int, default=40, help="disjoint copies of the mesh in the large components timing")
@@ -117,6 +121,12 @@ def main() -> int:
         os.makedirs(os.path.dirname(os.path.abspath(args.components_out)), exist_ok=True)
         with open(args.components_out, "w") as f:
             f.write(report)
+    if args.smooth_out:
+        report = smooth_report(args, exporter, state["volume"], mesh)
+        print(report)
+        os.makedirs(os.path.dirname(os.path.abspath(args.smooth_out)), exist_ok=True)
+        with open(args.smooth_out, "w") as f:
+            f.write(report)
     return 0
 
 
@@ -140,17 +150,14 @@ def event_ms(fn, repeats: int, calls: int):
     return per_call[len(per_call) // 2], per_call[0], per_call[-1]
 
 
-def components_report(args, exporter, volume, mesh, extract_pass_ms: float) -> str:
+def extract_call_of(exporter, volume, mesh):
+    """one emitting tn_mesh_extract call into the mesh's own buffers: the yardstick of the two kernel reports"""
     import torch
 
-    from thermo_nerf_amd import _hip, colormaps
+    from thermo_nerf_amd import colormaps
     from thermo_nerf_amd.export import mesh_extract, mesh_workspace_bytes
-    from thermo_nerf_amd.export.components import mesh_components_workspace_bytes
 
-    lib, dev = _hip.load(), mesh.triangles.device
-    v, t = len(mesh), int(mesh.triangles.shape[0])
-
-    # one emitting tn_mesh_extract call into the mesh's own buffers
+    dev = mesh.triangles.device
     counts = torch.zeros((2,), dtype=torch.int64, device=dev)
     ws = torch.empty((mesh_workspace_bytes(exporter.dims),), dtype=torch.uint8, device=dev)
     table = colormaps.get_table(exporter.thermal_color_map, dev)[1]
@@ -158,6 +165,19 @@ def components_report(args, exporter, volume, mesh, extract_pass_ms: float) -> s
     def extract_call():
         mesh_extract(volume, exporter.params, counts=counts, positions=mesh.positions, colors=mesh.colors, temperature=mesh.temperature,
                      thermal_colors=mesh.thermal_colors, thermal_table=table, triangles=mesh.triangles, workspace=ws)
+
+    return extract_call
+
+
+def components_report(args, exporter, volume, mesh, extract_pass_ms: float) -> str:
+    import torch
+
+    from thermo_nerf_amd import _hip
+    from thermo_nerf_amd.export.components import mesh_components_workspace_bytes
+
+    lib, dev = _hip.load(), mesh.triangles.device
+    v, t = len(mesh), int(mesh.triangles.shape[0])
+    extract_call = extract_call_of(exporter, volume, mesh)
 
     def components_call_on(tri, nv):
         nt = int(tri.shape[0])
@@ -195,6 +215,56 @@ def components_report(args, exporter, volume, mesh, extract_pass_ms: float) -> s
         lines.append(f"{name:43s} {nv:9d} {int(tri.shape[0]):11d}  {found:10d}  {f'{kv} / {kt}':19s} {c[0]:9.4f}   {c[1]:.4f} .. {c[2]:.4f}")
     lines.append(f"(MeshExporter.extract of the same run — sizing call, host read, allocation, emitting call — by the host clock: "
                  f"{extract_pass_ms:.3f} ms, median)")
+    return "\n".join(lines) + "\n"
+
+
+def smooth_report(args, exporter, volume, mesh, iterations: int = 10) -> str:
+    import torch
+
+    from thermo_nerf_amd import _hip
+    from thermo_nerf_amd.export import mesh_incidence_workspace_bytes
+
+    lib, dev = _hip.load(), mesh.triangles.device
+    v, t = len(mesh), int(mesh.triangles.shape[0])
+    extract_call = extract_call_of(exporter, volume, mesh)
+    source = mesh.positions.clone()  # the extract call rewrites the mesh's own positions with the same values
+
+    def calls_on(pos, tri):
+        nv, nt = int(pos.shape[0]), int(tri.shape[0])
+        offsets = torch.empty((nv + 1,), dtype=torch.int32, device=dev)
+        corners = torch.empty((3 * nt,), dtype=torch.int32, device=dev)
+        ws = torch.empty((mesh_incidence_workspace_bytes(nv, nt),), dtype=torch.uint8, device=dev)
+        normals, out, scratch = (torch.empty((nv, 3), dtype=torch.float32, device=dev) for _ in range(3))
+        stream = _hip.current_stream()
+
+        def incidence():  # the C entries directly, into preallocated outputs
+            _hip.check(lib.tn_mesh_incidence(tri.data_ptr(), nt, nv, offsets.data_ptr(), corners.data_ptr(), ws.data_ptr(), ws.numel(),
+                                             stream), "tn_mesh_incidence")
+
+        def vertex_normals():
+            _hip.check(lib.tn_mesh_vertex_normals(pos.data_ptr(), tri.data_ptr(), nt, nv, offsets.data_ptr(), corners.data_ptr(),
+                                                  normals.data_ptr(), stream), "tn_mesh_vertex_normals")
+
+        def smooth():
+            _hip.check(lib.tn_mesh_smooth(pos.data_ptr(), tri.data_ptr(), nt, nv, offsets.data_ptr(), corners.data_ptr(), iterations, 0.5,
+                                          -0.53, out.data_ptr(), scratch.data_ptr(), stream), "tn_mesh_smooth")
+
+        return (("tn_mesh_incidence", incidence), ("tn_mesh_vertex_normals", vertex_normals),
+                (f"tn_mesh_smooth, {iterations} iterations", smooth))
+
+    nx, ny, nz = exporter.dims
+    lines = [f"incidence index, vertex normals and Taubin smoothing of the mesh of tools/mesh_bench.py ({nx} x {ny} x {nz} volume, {args.poses} "
+             f"poses, S = {args.samples}), each entry timed on its own into preallocated outputs, beside one emitting tn_mesh_extract call; "
+             f"device events, 3 warm-up calls, {args.repeats} windows of {args.calls} back-to-back calls, ms per call",
+             "what                                                      vertices   triangles   median ms   min .. max"]
+    e = event_ms(extract_call, args.repeats, args.calls)
+    lines.append(f"{'tn_mesh_extract (emitting call)':57s} {v:9d} {t:11d} {e[0]:9.4f}   {e[1]:.4f} .. {e[2]:.4f}")
+    big_tri = torch.cat([mesh.triangles + k * v for k in range(args.copies)]) if t else mesh.triangles
+    big_pos = torch.cat([source + float(k) for k in range(args.copies)])
+    for label, pos, tri in (("the mesh", source, mesh.triangles), (f"{args.copies} disjoint copies", big_pos, big_tri)):
+        for name, call in calls_on(pos, tri):  # in this order: the index is built before the entries that read it
+            c = event_ms(call, args.repeats, args.calls)
+            lines.append(f"{f'{name}, {label}':57s} {int(pos.shape[0]):9d} {int(tri.shape[0]):11d} {c[0]:9.4f}   {c[1]:.4f} .. {c[2]:.4f}")
     return "\n".join(lines) + "\n"
 
 
