@@ -1089,7 +1089,20 @@ int tn_train_step_bwd(const tn_train_step_bwd_args *a);
  * with the step-dependent scalars formed by the caller (step_size = lr / (1 - beta1^t), bias_correction2_sqrt =
  * sqrt(1 - beta2^t), t = the tensor's own step count): tensors of different groups and step counts share a launch.
  * `tensors` is a HOST array of `count` <= TN_ADAM_MAX_TENSORS descriptors (device pointers inside); param / exp_avg /
- * exp_avg_sq are updated in place, grad is read only; tensors with n = 0 are skipped. */
+ * exp_avg_sq are updated in place, grad is read only; tensors with n = 0 are skipped (their pointers may be NULL).  The four
+ * pointers need no alignment beyond a float's and may differ in it.
+ * THE RESULT IS DEFINED: every output float is the following sequence of correctly rounded fp32 operations (round to nearest
+ * even, no contraction) on the element's four inputs and the descriptor's seven scalars, one operation per line item:
+ *     g' = grad + weight_decay * param                      product, sum          (skipped when weight_decay == 0: g' = grad)
+ *     m' = exp_avg + (g' - exp_avg) * one_minus_beta1       difference, product, sum
+ *     v' = beta2 * exp_avg_sq + (one_minus_beta2 * g') * g' product | product, product | sum
+ *     den = sqrt(v') / bias_correction2_sqrt + eps          root, quotient, sum
+ *     param' = param - step_size * (m' / den)               quotient, product, difference
+ * exp_avg <- m', exp_avg_sq <- v', param <- param'.  Subnormal operands and results are kept, in every operation (v' of a
+ * gradient of 1e-20 is one).  Where the sequence gives a NaN (an inf or NaN gradient; 0 / 0 with zero moments, zero gradient and
+ * eps == 0) the output is a NaN whose sign and payload are not defined; no other element is affected.  Nothing outside
+ * [0, n) of any array is read or written.  tests/adam_reference.py restates the sequence; tests/test_gpu_adam.py asserts it bit
+ * for bit. */
 #define TN_ADAM_MAX_TENSORS 32
 typedef struct tn_adam_tensor {
     float *param;

@@ -29,16 +29,19 @@ struct AdamList {
     int32_t count;
 };
 
+// Every line below is one correctly rounded fp32 operation per intrinsic, in this order (include/thermonerf_hip.h declares the
+// sequence as the result; tests/adam_reference.py restates it).  The root is sqrtf, which hipcc expands to v_sqrt_f32 plus a
+// one-ulp correction from the residual, scaled for subnormal arguments: HIP's __fsqrt_rn is the bare v_sqrt_f32 (1 ulp).
 __device__ __forceinline__ void adam_one(float &p, float g, float &m, float &v, const tn_adam_tensor &t) {
     if (t.weight_decay != 0.0f) g = __fadd_rn(g, __fmul_rn(t.weight_decay, p));
     m = __fadd_rn(m, __fmul_rn(__fsub_rn(g, m), t.one_minus_beta1));
     v = __fadd_rn(__fmul_rn(t.beta2, v), __fmul_rn(__fmul_rn(t.one_minus_beta2, g), g));
-    const float denom = __fadd_rn(__fdiv_rn(__fsqrt_rn(v), t.bias_correction2_sqrt), t.eps);
+    const float denom = __fadd_rn(__fdiv_rn(__builtin_sqrtf(v), t.bias_correction2_sqrt), t.eps);
     p = __fsub_rn(p, __fmul_rn(t.step_size, __fdiv_rn(m, denom)));
 }
 
 __global__ void __launch_bounds__(kBlock) adam_kernel(AdamList L) {
-    // which tensor: a linear walk over <= 48 block offsets held in SGPRs (uniform per block)
+    // which tensor: a linear walk over <= TN_ADAM_MAX_TENSORS block offsets held in SGPRs (uniform per block)
     int k = 0;
     while (k + 1 < L.count && (int)blockIdx.x >= L.first_block[k + 1]) ++k;
     const tn_adam_tensor t = L.t[k];

@@ -14,7 +14,9 @@ stream, behind the field's table-gradient scatter.  Here:
 * state layout and ``state_dict`` are torch.optim.Adam's (``step`` / ``exp_avg`` / ``exp_avg_sq`` per parameter), so a checkpoint
   written by either loads into the other.
 
-Same update rule as torch's (L2 weight decay, bias corrections in float64 on the host), rounding may differ in the last bit.
+Same update rule as torch's (L2 weight decay, bias corrections in float64 on the host), rounding may differ in the last bit: every
+output float is the sequence of correctly rounded fp32 operations include/thermonerf_hip.h declares at tn_adam_step, on the seven
+scalars ``_slot`` forms in float64 and the descriptor's float fields round once (tests/test_gpu_adam.py asserts it bit for bit).
 No CPU path: parameters must live on a ROCm device.
 """
 from __future__ import annotations
