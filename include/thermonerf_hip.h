@@ -615,6 +615,20 @@ typedef struct tn_render_config {
      * stratified draw per ray and level, tn_render_inputs.jitter = [3,R]; 1 = single_jitter=False: one draw per bin edge,
      * jitter = [R,P0+1] | [R,P1+1] | [R,S+1] back to back [NS SpacedSampler / PDFSampler.generate_ray_samples]. */
     int32_t per_sample_jitter;
+    /* The last partial round of tiles of a whole-march call of the exact-fp32 lane = ray field kernel (eval; appended, 0 keeps
+     * "the library decides").  A call of T tiles on 2 048 wave slots lasts ceil(T / 2048) tile-times: the 800 x 800 frame's
+     * 10 000 tiles last five, the fifth with 1 808 of the slots busy.  Those T mod 2048 tiles can instead be evaluated as
+     * (tile, segment) units that only RECORD (delta * density, r, g, b, thermal) per sample, and composited by a replay pass
+     * that runs the serial march's own statements on the records: the same bits in every output, unlike sample_split.
+     * 0 = by call shape (tn_render_tail_plan), 1 = never, k > 1 = k segments per tile (fewer where a segment would be shorter
+     * than 12 samples; tn_render_tail_plan reports the value used).  Applies only to calls of at least one whole round with a
+     * remainder, without early termination and not in the sample_split form; the records (5 x 4 B per ray and sample) live
+     * behind the proposal scratch of the workspace (tn_render_workspace_bytes counts them; a workspace that ends before them
+     * makes the call march whole tiles). */
+    int32_t tail_balance;
+    /* TEST HOOK for the above, 0 in production: the number of wave slots the lane = ray field kernel is launched on (a multiple of
+     * 8: 16 = a grid of two blocks), so that a few thousand rays make whole rounds plus a remainder. */
+    int32_t tail_slots;
 } tn_render_config;
 
 typedef struct tn_render_inputs {
@@ -694,6 +708,17 @@ int32_t tn_render_kernel_form(const tn_thermal_field *field, const tn_render_con
  * cfg->sample_split (see there).  Like the kernel form it is a property of the CALL: a caller that renders part of a launch and
  * wants the whole launch's bits passes the whole launch's value as cfg->sample_split. */
 int32_t tn_render_sample_split(const tn_thermal_field *field, const tn_render_config *cfg, int64_t num_rays);
+/* Segments per tile for the last partial round (tn_render_config.tail_balance) of `tiles` tiles on `slots` wave slots at
+ * num_samples samples per ray; 1 = march whole tiles.  request 0: the k in 2..16 with segments of at least 12 samples that
+ * minimises ceil(rem k / slots) / k, rem = tiles mod slots (the smallest such k), unless even that is above 0.95; request
+ * k > 1: k, or fewer where the segments would be shorter than 12 samples.  Always 1 when tiles < slots (such calls belong to
+ * sample_split) or rem == 0.  A pure function: (10 000, 2 048, 192) -> 9, 1 808 x 9 units = 7.95 rounds of one ninth. */
+int32_t tn_render_tail_segments(int64_t tiles, int64_t slots, int32_t num_samples, int32_t request);
+/* The same for a call of tn_field_render_fwd / _chunked_fwd under cfg (tail_balance, tail_slots, early termination, training,
+ * kernel form, sample_split) on `field`; field == NULL: as for an exact-fp32 field (what tn_render_workspace_bytes assumes). */
+int32_t tn_render_tail_plan(const tn_thermal_field *field, const tn_render_config *cfg, int64_t num_rays);
+/* The bytes of records at the end of tn_render_workspace_bytes(cfg, num_rays): 0 where the plan is 1. */
+size_t tn_render_tail_records_bytes(const tn_render_config *cfg, int64_t num_rays);
 int tn_field_render_chunked_fwd(const tn_thermal_field *field, const tn_render_config *cfg, const tn_render_inputs *in,
                                 const tn_render_outputs *out, int64_t num_rays, void *workspace, size_t workspace_bytes,
                                 int64_t first_ray, int64_t chunk_rays, float *depth_bounds, int32_t clip, void *stream);

@@ -140,6 +140,8 @@ class tn_render_config(C.Structure):
         ("initial_sampler", C.c_int32),
         ("sample_split", C.c_int32),
         ("per_sample_jitter", C.c_int32),
+        ("tail_balance", C.c_int32),
+        ("tail_slots", C.c_int32),
     ]
 
 
@@ -272,6 +274,9 @@ SIGNATURES = {
     "tn_depth_bound_slots": (_i64, [_i64, _i64, _i64]),
     "tn_render_kernel_form": (C.c_int32, [C.POINTER(tn_thermal_field), C.POINTER(tn_render_config), _i64, C.c_int32]),
     "tn_render_sample_split": (C.c_int32, [C.POINTER(tn_thermal_field), C.POINTER(tn_render_config), _i64]),
+    "tn_render_tail_segments": (C.c_int32, [_i64, _i64, C.c_int32, C.c_int32]),
+    "tn_render_tail_plan": (C.c_int32, [C.POINTER(tn_thermal_field), C.POINTER(tn_render_config), _i64]),
+    "tn_render_tail_records_bytes": (_sz, [C.POINTER(tn_render_config), _i64]),
     "tn_field_render_chunked_fwd": (
         C.c_int,
         [C.POINTER(tn_thermal_field), C.POINTER(tn_render_config), C.POINTER(tn_render_inputs),

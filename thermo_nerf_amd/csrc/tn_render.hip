@@ -41,7 +41,7 @@ namespace tn {
 // implemented in tn_render_mfma.hip
 int launch_main_mfma(const tn_thermal_field *field, const tn_render_config *cfg, const tn_render_inputs *in,
                      const tn_render_outputs *out, long long num_rays, const float *spacing_ws, DepthSlots minmax,
-                     hipStream_t stream, int split, float *seg_scratch);
+                     hipStream_t stream, int split, float *seg_scratch, int tail_k, float *tail_rec, int tail_slots);
 // implemented in tn_render_h3.hip (the two split-precision policies of one kernel)
 int launch_main_b6(const tn_thermal_field *field, const tn_render_config *cfg, const tn_render_inputs *in,
                    const tn_render_outputs *out, long long num_rays, const float *spacing_ws, DepthSlots minmax,
@@ -872,7 +872,7 @@ inline unsigned ray_grid(long long R, int blocks_per_cu) {
 
 extern "C" {
 
-size_t tn_render_workspace_bytes(const tn_render_config *cfg, int64_t num_rays) {
+static size_t render_workspace_base_bytes(const tn_render_config *cfg, int64_t num_rays) {
     if (!cfg || num_rays < 0) return 0;
     // [final edges, ray-tiled] [kWsMid B: depth min/max (8 B) | at +256: the proposal MLPs' k-major weight copies]
     // [proposal scratch: level weights + level-1 edges, ray-tiled]
@@ -883,12 +883,19 @@ size_t tn_render_workspace_bytes(const tn_render_config *cfg, int64_t num_rays) 
            tiles * 64 * (nmax + (size_t)P1 + 1) * sizeof(float);
 }
 
+// ... [the records of the field pass's last partial round (tn_render_tail_plan), 256-byte aligned]
+size_t tn_render_workspace_bytes(const tn_render_config *cfg, int64_t num_rays) {
+    if (!cfg || num_rays < 0) return 0;
+    const size_t rec = tn_render_tail_records_bytes(cfg, num_rays);
+    return rec ? align_up(render_workspace_base_bytes(cfg, num_rays), 256) + rec : render_workspace_base_bytes(cfg, num_rays);
+}
+
 static int check_render_common(const tn_render_config *cfg, int64_t num_rays, void *workspace, size_t workspace_bytes) {
     if (!cfg || !workspace) return TN_ERR_NULL;
     const int P0 = cfg->num_proposal_samples[0], P1 = cfg->num_proposal_samples[1], S = cfg->num_nerf_samples;
     if (P0 < 1 || P1 < 1 || S < 1 || P0 > 1024 || P1 > 1024 || S > 1024 || num_rays < 0) return TN_ERR_SHAPE;
     if (cfg->initial_sampler != 0 && cfg->initial_sampler != 1) return TN_ERR_UNSUPPORTED;
-    if (workspace_bytes < tn_render_workspace_bytes(cfg, num_rays)) return TN_ERR_WORKSPACE;
+    if (workspace_bytes < render_workspace_base_bytes(cfg, num_rays)) return TN_ERR_WORKSPACE;  // (the tail records are optional)
     return TN_OK;
 }
 
@@ -1055,7 +1062,14 @@ static int field_render_fwd(const tn_thermal_field *field, const tn_render_confi
         const int split = out->weights[2] ? 1 : tn_render_sample_split(field, cfg, num_rays);
         float *seg_scratch = reinterpret_cast<float *>(reinterpret_cast<char *>(workspace) +
                                                        align_up(tn_ws_bin_floats(num_rays, S) * sizeof(float), 256) + kWsMid);
-        TN_TRY(launch_main_mfma(field, cfg, in, out, (long long)num_rays, ws_spacing, minmax, s, split, seg_scratch));
+        // the last partial round as records + replay (tn_render_tail_plan), where the caller's workspace reaches that far
+        int tail_k = tn_render_tail_plan(field, cfg, num_rays);
+        const size_t rec_off = align_up(render_workspace_base_bytes(cfg, num_rays), 256);
+        const size_t rec_bytes = tn_render_tail_records_bytes(cfg, num_rays);
+        if (out->weights[2] || rec_bytes == 0 || workspace_bytes < rec_off + rec_bytes) tail_k = 1;
+        float *tail_rec = reinterpret_cast<float *>(reinterpret_cast<char *>(workspace) + rec_off);
+        TN_TRY(launch_main_mfma(field, cfg, in, out, (long long)num_rays, ws_spacing, minmax, s, split, seg_scratch, tail_k, tail_rec,
+                                cfg->tail_slots));
     } else {
         MainArgs ma;
         ma.g = tn_make_grid(field->grid);
@@ -1145,6 +1159,54 @@ int32_t tn_render_sample_split(const tn_thermal_field *field, const tn_render_co
     for (int k = 2; k <= kmax; ++k)
         if (100 * cost[k] <= 107 * best_cost) best = k;
     return best;
+}
+
+static inline int64_t tail_slots_of(const tn_render_config *cfg) {
+    return cfg->tail_slots > 0 ? ((int64_t)cfg->tail_slots + 7) / 8 * 8 : 2048;  // 256 CUs x one block of 8 waves
+}
+
+int32_t tn_render_tail_segments(int64_t tiles, int64_t slots, int32_t num_samples, int32_t request) {
+    constexpr int kMinSeg = 12, kMaxK = 16;
+    if (tiles <= 0 || slots <= 0 || num_samples < 1 || request == 1 || request < 0) return 1;
+    const int64_t rem = tiles % slots;
+    if (tiles < slots || rem == 0) return 1;
+    const int S = num_samples;
+    // k segments of ceil(S / k) samples, of which ceil(S / len) are not empty
+    auto used = [S](int k) { const int len = (S + k - 1) / k; return (S + len - 1) / len; };
+    int kcap = S / kMinSeg;  // the most segments of at least kMinSeg samples
+    if (kcap > kMaxK) kcap = kMaxK;
+    if (request > 1) {
+        const int k = request < kcap ? request : kcap;
+        return k < 2 ? 1 : used(k);
+    }
+    int best = 1;
+    int64_t best_rounds = 1;  // rounds / k of the best so far, compared as cross products; whole tiles: 1 / 1
+    for (int k = 2; k <= kcap; ++k) {
+        if (used(k) != k) continue;
+        const int64_t rounds = (rem * k + slots - 1) / slots;
+        if (rounds * best < best_rounds * k) { best = k; best_rounds = rounds; }
+    }
+    return 100 * best_rounds > 95 * best ? 1 : best;
+}
+
+// field == nullptr: the cfg-only view (as on an exact-fp32 field), which is what the workspace query can know
+int32_t tn_render_tail_plan(const tn_thermal_field *field, const tn_render_config *cfg, int64_t num_rays) {
+    if (!cfg || num_rays <= 0 || cfg->tail_balance == 1 || cfg->tail_balance < 0) return 1;
+    if (cfg->training || cfg->early_stop_transmittance > 0.0f) return 1;
+    if (field && (!field->prepared || field->prepared_bf16x6 || field->prepared_f16x3)) return 1;
+    tn_thermal_field exact{};
+    if (!field) {  // (only `prepared` and the split-precision pointers are read by the two queries below)
+        exact.prepared = reinterpret_cast<decltype(exact.prepared)>(&exact);
+        field = &exact;
+    }
+    if (tn_render_kernel_form(field, cfg, num_rays, 1) != 1 || tn_render_sample_split(field, cfg, num_rays) != 1) return 1;
+    return tn_render_tail_segments((num_rays + 63) / 64, tail_slots_of(cfg), cfg->num_nerf_samples, cfg->tail_balance);
+}
+
+size_t tn_render_tail_records_bytes(const tn_render_config *cfg, int64_t num_rays) {
+    if (tn_render_tail_plan(nullptr, cfg, num_rays) < 2) return 0;
+    const int64_t tiles = (num_rays + 63) / 64;
+    return (size_t)(tiles % tail_slots_of(cfg)) * (size_t)cfg->num_nerf_samples * 5 * 64 * sizeof(float);
 }
 
 int64_t tn_depth_bound_slots(int64_t first_ray, int64_t num_rays, int64_t chunk_rays) {

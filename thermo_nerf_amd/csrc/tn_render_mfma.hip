@@ -648,11 +648,10 @@ __device__ unsigned int tn_field_stamp_buf[kStampBlocks * 2 * kStampSamples * kS
 #define TN_STAMP(k) do { } while (0)
 #endif
 
-template <bool DENSE, bool SPLIT = false>
-__global__ void __launch_bounds__(kRaysBlock, 1) main_mfma_rays_kernel(MfmaArgs a) {
-    extern __shared__ __attribute__((aligned(16))) float lds[];
+// the lane = ray field kernels' LDS image of the prepared blob (the SH / appearance rows are per tile, not per sample: left out)
+__device__ __forceinline__ void rays_stage_blob(float *lds, const float *blob) {
     {
-        const float4 *src = reinterpret_cast<const float4 *>(a.blob);
+        const float4 *src = reinterpret_cast<const float4 *>(blob);
         float4 *dst = reinterpret_cast<float4 *>(lds);
         for (int i = threadIdx.x; i < RAYS_BLOB_FLOATS / 4; i += kRaysBlock) {
             float4 v = src[i < OFF_W_SH / 4 ? i : i + (OFF_W3 - OFF_W_SH) / 4];
@@ -665,8 +664,150 @@ __global__ void __launch_bounds__(kRaysBlock, 1) main_mfma_rays_kernel(MfmaArgs 
             dst[i] = v;
         }
     }
-    __syncthreads();
+}
+
+// per-tile colour-layer bias of 64 rays (see main_mfma_rays_kernel): c0[0][0] returned in registers, the other three tiles in the
+// lane's LDS slots
+__device__ __forceinline__ void rays_tile_bias(const float *lds, int lane, int h, int sh_shifted, float dx, float dy, float dz,
+                                               float4 *c0s, f32x16 &c00) {
+    f32x16 c0[2][2];
+    float sx = dx, sy = dy, sz = dz;
+    if (sh_shifted) {
+        sx = add_rn(sx, 1.0f) / 2.0f; sy = add_rn(sy, 1.0f) / 2.0f; sz = add_rn(sz, 1.0f) / 2.0f;
+    }
+    float c[16];
+    sh16(sx, sy, sz, c);
+#pragma unroll
+    for (int mt = 0; mt < 2; ++mt) {
+        c0[mt][0] = bias_frag(lds + OFF_B_C1_EVAL, mt, h);
+        c0[mt][1] = c0[mt][0];
+    }
+#pragma unroll
+    for (int s = 0; s < 8; ++s) {
+        float bs0, bs1;
+        swap32(c[2 * s], c[2 * s + 1], bs0, bs1);
+#pragma unroll
+        for (int mt = 0; mt < 2; ++mt) {
+            const float aw = lds[OFF_A + (A_SH + mt * 8 + s) * 64 + lane];
+            MFMA32(c0[mt][0], aw, bs0);
+            MFMA32(c0[mt][1], aw, bs1);
+        }
+    }
+    c00 = c0[0][0];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        c0s[(0 + q) * 64] = make_float4(c0[0][1][4 * q], c0[0][1][4 * q + 1], c0[0][1][4 * q + 2], c0[0][1][4 * q + 3]);
+        c0s[(4 + q) * 64] = make_float4(c0[1][0][4 * q], c0[1][0][4 * q + 1], c0[1][0][4 * q + 2], c0[1][0][4 * q + 3]);
+        c0s[(8 + q) * 64] = make_float4(c0[1][1][4 * q], c0[1][1][4 * q + 1], c0[1][1][4 * q + 2], c0[1][1][4 * q + 3]);
+    }
+}
+
+// ONE sample of a 64-ray tile, shared by the whole-march kernels and field_records_kernel: bin edges -> mid-point position ->
+// hash phase -> base MLP -> density | colour and thermal heads; cr, cg, cb, th after the eval renderers' nan_to_num.  `en` and
+// `sb_next` carry the edge pipeline from sample to sample (en: this sample's start on entry, its end on exit).
+#if TN_FIELD_STAMPS
+#define TN_STAMP_PARAM , unsigned int (&stamp)[kStampSlots]
+#define TN_STAMP_ARG , stamp
+#else
+#define TN_STAMP_PARAM
+#define TN_STAMP_ARG
+#endif
+template <bool DENSE>
+__device__ __forceinline__ void field_sample(const Grid &g_, const Space &sp, const float *lds, int lane, int h, const float4 *c0s,
+                                             const f32x16 &c00, float ox, float oy, float oz, float dx, float dy, float dz, float s_near,
+                                             float s_far, bool lin, const float *tb, int i, int S, float avg, float &en, float &sb_next,
+                                             float &st, float &step, float &dens, float &cr, float &cg, float &cb,
+                                             float &th TN_STAMP_PARAM) {
     const float *A = lds + OFF_A;
+    st = en;
+    en = spacing_to_eucl<true>(sb_next, s_near, s_far, lin);
+    sb_next = tb[(size_t)(i + 2 <= S ? i + 2 : S) * 64];
+    step = add_rn(st, en) / 2.0f;
+    float px, py, pz;
+    const float sel = normalize_position<true>(sp, frustum_pos(ox, dx, st, en), frustum_pos(oy, dy, st, en),
+                                         frustum_pos(oz, dz, st, en), px, py, pz);
+    float bt0[16], bt1[16];
+    // index arithmetic | gathers | interpolation in explicit stages, two groups of LG levels in flight; DENSE: the first
+    // kFieldDense levels come from the dense re-layout (4 aligned 16-byte gathers per level instead of 8 8-byte ones)
+#if TN_FIELD_STAMPS
+    hash_encode_pipelined_raw<L16, LG, DENSE ? kFieldDense : 0, TN_EVAL_GATHER_PRIO>(
+        g_, px, py, pz, [&](int l, const HashTaps &t, const float2 (&fc)[8]) {
+            if (l % LG == 0) TN_STAMP(1 + 2 * (l / LG));
+            const float2 f = hash_blend(t, fc);
+            if (l % LG == 0) TN_STAMP(2 + 2 * (l / LG));
+            swap32(f.x, f.y, bt0[l], bt1[l]);
+        });
+    TN_STAMP(9);
+#else
+    hash_encode_pipelined<L16, LG, DENSE ? kFieldDense : 0, TN_EVAL_GATHER_PRIO>(g_, px, py, pz,
+                                                            [&](int l, float2 f) { swap32(f.x, f.y, bt0[l], bt1[l]); });
+#endif
+#if TN_MFMA_MLP_PRIO
+    __builtin_amdgcn_s_setprio(TN_MFMA_MLP_PRIO);
+#endif
+    f32x16 h1[2][2];
+#pragma unroll
+    for (int mt = 0; mt < 2; ++mt) {
+        h1[mt][0] = bias_frag(lds + OFF_B_BASE1, mt, h);
+        h1[mt][1] = h1[mt][0];
+    }
+#pragma unroll
+    for (int s = 0; s < 16; ++s) {
+#pragma unroll
+        for (int mt = 0; mt < 2; ++mt) {
+            const float aw = A[(A_BASE1 + mt * 16 + s) * 64 + lane];
+            MFMA32(h1[mt][0], aw, bt0[s]);
+            MFMA32(h1[mt][1], aw, bt1[s]);
+        }
+    }
+    float g[2][8];
+    base2_geo<TN_BASE2_STAGED != 0>(A, lds + OFF_B_BASE2, lane, h1, g);
+    float raw, unused;
+    swap32(g[0][0], g[1][0], raw, unused);
+    dens = mul_rn(mul_rn(avg, __expf(raw)), sel);
+    TN_STAMP(10);
+    {   // colour: geo (on the per-ray bias c0) -> 64 -> 64 -> 3
+        f32x16 x1[2][2] = {{c00, c0_frag(c0s)}, {c0_frag(c0s + 4 * 64), c0_frag(c0s + 8 * 64)}}, x2[2][2];
+#pragma unroll
+        for (int s = 0; s < 8; ++s) {
+#pragma unroll
+            for (int mt = 0; mt < 2; ++mt) {
+                const float aw = A[(A_C1 + mt * 8 + s) * 64 + lane];
+                MFMA32(x1[mt][0], aw, g[0][s]);
+                MFMA32(x1[mt][1], aw, g[1][s]);
+            }
+        }
+        layer64(A, A_C2, lds + OFF_B_C2, lane, h, x1, x2);
+        TN_STAMP(11);
+        const float *w3 = lds + RAYS_OFF_W3;
+        cr = fast_sigmoid(combine_halves(out_dot_fast<0>(w3, h, x2)) + w3[192]);
+        cg = fast_sigmoid(combine_halves(out_dot_fast<0>(w3 + 64, h, x2)) + w3[193]);
+        cb = fast_sigmoid(combine_halves(out_dot_fast<0>(w3 + 128, h, x2)) + w3[194]);
+        TN_STAMP(12);
+    }
+#if TN_MFMA_THERMAL_PRIO != TN_MFMA_MLP_PRIO
+    __builtin_amdgcn_s_setprio(TN_MFMA_THERMAL_PRIO);
+#endif
+    {   // thermal: geo -> 64 -> 64 sigmoid -> 1
+        f32x16 x1[2][2], x2[2][2];
+        layer_geo(A, A_T1, lds + OFF_B_T1, lane, h, g, x1);
+        layer64(A, A_T2, lds + OFF_B_T2, lane, h, x1, x2);
+        TN_STAMP(13);
+        const float *wt = lds + RAYS_OFF_WTH;
+        th = combine_halves(out_dot_fast<TN_T2_PRESCALE ? 2 : 1>(wt, h, x2)) + wt[64];
+        TN_STAMP(14);
+    }
+#if TN_MFMA_MLP_PRIO
+    __builtin_amdgcn_s_setprio(0);
+#endif
+    cr = nan_to_num(cr); cg = nan_to_num(cg); cb = nan_to_num(cb); th = nan_to_num(th);  // eval renderers
+}
+
+template <bool DENSE, bool SPLIT = false>
+__global__ void __launch_bounds__(kRaysBlock, 1) main_mfma_rays_kernel(MfmaArgs a) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    rays_stage_blob(lds, a.blob);
+    __syncthreads();
     const Space sp = make_space(a.space);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, h = lane >> 5;
     const bool lin = a.lin != 0;
@@ -705,38 +846,7 @@ __global__ void __launch_bounds__(kRaysBlock, 1) main_mfma_rays_kernel(MfmaArgs 
         // the 8 SH k-steps run once per tile; c0[0][0] stays in registers as the C operand of every sample's first colour MFMA, the
         // other three tiles go to this lane's LDS slots and are read back into the layer's accumulators at every sample
         f32x16 c00;
-        {
-            f32x16 c0[2][2];
-            float sx = dx, sy = dy, sz = dz;
-            if (a.sh_shifted) {
-                sx = add_rn(sx, 1.0f) / 2.0f; sy = add_rn(sy, 1.0f) / 2.0f; sz = add_rn(sz, 1.0f) / 2.0f;
-            }
-            float c[16];
-            sh16(sx, sy, sz, c);
-#pragma unroll
-            for (int mt = 0; mt < 2; ++mt) {
-                c0[mt][0] = bias_frag(lds + OFF_B_C1_EVAL, mt, h);
-                c0[mt][1] = c0[mt][0];
-            }
-#pragma unroll
-            for (int s = 0; s < 8; ++s) {
-                float bs0, bs1;
-                swap32(c[2 * s], c[2 * s + 1], bs0, bs1);
-#pragma unroll
-                for (int mt = 0; mt < 2; ++mt) {
-                    const float aw = A[(A_SH + mt * 8 + s) * 64 + lane];
-                    MFMA32(c0[mt][0], aw, bs0);
-                    MFMA32(c0[mt][1], aw, bs1);
-                }
-            }
-            c00 = c0[0][0];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                c0s[(0 + q) * 64] = make_float4(c0[0][1][4 * q], c0[0][1][4 * q + 1], c0[0][1][4 * q + 2], c0[0][1][4 * q + 3]);
-                c0s[(4 + q) * 64] = make_float4(c0[1][0][4 * q], c0[1][0][4 * q + 1], c0[1][0][4 * q + 2], c0[1][0][4 * q + 3]);
-                c0s[(8 + q) * 64] = make_float4(c0[1][1][4 * q], c0[1][1][4 * q + 1], c0[1][1][4 * q + 2], c0[1][1][4 * q + 3]);
-            }
-        }
+        rays_tile_bias(lds, lane, h, a.sh_shifted, dx, dy, dz, c0s, c00);
         float en = spacing_to_eucl<true>(tb[(size_t)s0 * 64], s_near, s_far, lin);
         float accum = 0.0f, cum_w = 0.0f;  // sum of delta*sigma before this sample; running sum of weights
         float wsum = 0.0f, wr = 0.0f, wg = 0.0f, wbl = 0.0f, wth = 0.0f, wsteps = 0.0f;
@@ -747,88 +857,9 @@ __global__ void __launch_bounds__(kRaysBlock, 1) main_mfma_rays_kernel(MfmaArgs 
         float sb_next = tb[(size_t)(s0 + 1) * 64];
         for (int i = s0; i < s1; ++i) {
             TN_STAMP(0);
-            const float st = en;
-            en = spacing_to_eucl<true>(sb_next, s_near, s_far, lin);
-            sb_next = tb[(size_t)(i + 2 <= S ? i + 2 : S) * 64];
-            step = add_rn(st, en) / 2.0f;
-            float px, py, pz;
-            const float sel = normalize_position<true>(sp, frustum_pos(ox, dx, st, en), frustum_pos(oy, dy, st, en),
-                                                 frustum_pos(oz, dz, st, en), px, py, pz);
-            float bt0[16], bt1[16];
-            // index arithmetic | gathers | interpolation in explicit stages, two groups of LG levels in flight; DENSE: the first
-            // kFieldDense levels come from the dense re-layout (4 aligned 16-byte gathers per level instead of 8 8-byte ones)
-#if TN_FIELD_STAMPS
-            hash_encode_pipelined_raw<L16, LG, DENSE ? kFieldDense : 0, TN_EVAL_GATHER_PRIO>(
-                a.g, px, py, pz, [&](int l, const HashTaps &t, const float2 (&fc)[8]) {
-                    if (l % LG == 0) TN_STAMP(1 + 2 * (l / LG));
-                    const float2 f = hash_blend(t, fc);
-                    if (l % LG == 0) TN_STAMP(2 + 2 * (l / LG));
-                    swap32(f.x, f.y, bt0[l], bt1[l]);
-                });
-            TN_STAMP(9);
-#else
-            hash_encode_pipelined<L16, LG, DENSE ? kFieldDense : 0, TN_EVAL_GATHER_PRIO>(a.g, px, py, pz,
-                                                                    [&](int l, float2 f) { swap32(f.x, f.y, bt0[l], bt1[l]); });
-#endif
-#if TN_MFMA_MLP_PRIO
-            __builtin_amdgcn_s_setprio(TN_MFMA_MLP_PRIO);
-#endif
-            f32x16 h1[2][2];
-#pragma unroll
-            for (int mt = 0; mt < 2; ++mt) {
-                h1[mt][0] = bias_frag(lds + OFF_B_BASE1, mt, h);
-                h1[mt][1] = h1[mt][0];
-            }
-#pragma unroll
-            for (int s = 0; s < 16; ++s) {
-#pragma unroll
-                for (int mt = 0; mt < 2; ++mt) {
-                    const float aw = A[(A_BASE1 + mt * 16 + s) * 64 + lane];
-                    MFMA32(h1[mt][0], aw, bt0[s]);
-                    MFMA32(h1[mt][1], aw, bt1[s]);
-                }
-            }
-            float g[2][8];
-            base2_geo<TN_BASE2_STAGED != 0>(A, lds + OFF_B_BASE2, lane, h1, g);
-            float raw, unused;
-            swap32(g[0][0], g[1][0], raw, unused);
-            const float dens = mul_rn(mul_rn(a.avg, __expf(raw)), sel);
-            TN_STAMP(10);
-            {   // colour: geo (on the per-ray bias c0) -> 64 -> 64 -> 3
-                f32x16 x1[2][2] = {{c00, c0_frag(c0s)}, {c0_frag(c0s + 4 * 64), c0_frag(c0s + 8 * 64)}}, x2[2][2];
-#pragma unroll
-                for (int s = 0; s < 8; ++s) {
-#pragma unroll
-                    for (int mt = 0; mt < 2; ++mt) {
-                        const float aw = A[(A_C1 + mt * 8 + s) * 64 + lane];
-                        MFMA32(x1[mt][0], aw, g[0][s]);
-                        MFMA32(x1[mt][1], aw, g[1][s]);
-                    }
-                }
-                layer64(A, A_C2, lds + OFF_B_C2, lane, h, x1, x2);
-                TN_STAMP(11);
-                const float *w3 = lds + RAYS_OFF_W3;
-                cr = fast_sigmoid(combine_halves(out_dot_fast<0>(w3, h, x2)) + w3[192]);
-                cg = fast_sigmoid(combine_halves(out_dot_fast<0>(w3 + 64, h, x2)) + w3[193]);
-                cb = fast_sigmoid(combine_halves(out_dot_fast<0>(w3 + 128, h, x2)) + w3[194]);
-                TN_STAMP(12);
-            }
-#if TN_MFMA_THERMAL_PRIO != TN_MFMA_MLP_PRIO
-            __builtin_amdgcn_s_setprio(TN_MFMA_THERMAL_PRIO);
-#endif
-            {   // thermal: geo -> 64 -> 64 sigmoid -> 1
-                f32x16 x1[2][2], x2[2][2];
-                layer_geo(A, A_T1, lds + OFF_B_T1, lane, h, g, x1);
-                layer64(A, A_T2, lds + OFF_B_T2, lane, h, x1, x2);
-                TN_STAMP(13);
-                const float *wt = lds + RAYS_OFF_WTH;
-                th = combine_halves(out_dot_fast<TN_T2_PRESCALE ? 2 : 1>(wt, h, x2)) + wt[64];
-                TN_STAMP(14);
-            }
-#if TN_MFMA_MLP_PRIO
-            __builtin_amdgcn_s_setprio(0);
-#endif
-            cr = nan_to_num(cr); cg = nan_to_num(cg); cb = nan_to_num(cb); th = nan_to_num(th);  // eval renderers
+            float st, dens;
+            field_sample<DENSE>(a.g, sp, lds, lane, h, c0s, c00, ox, oy, oz, dx, dy, dz, s_near, s_far, lin, tb, i, S, a.avg, en, sb_next,
+                                st, step, dens, cr, cg, cb, th TN_STAMP_ARG);
             // ---- per-lane compositing: NS get_weights + renderers, sequential along the ray ----------------
             const float dd = mul_rn(sub_rn(en, st), dens);
             const float wi = nan_to_num(mul_rn(sub_rn(1.0f, __expf(-dd)), __expf(-accum)));
@@ -941,6 +972,148 @@ __global__ void segments_combine_kernel(MfmaArgs a) {
     a.acc[r] = wsum;
     a.depth[r] = med_found ? med : step;
     a.expected[r] = wsteps / add_rn(wsum, 1e-10f);
+}
+
+// ------------------------------------------------------------------------------------------------------
+// The last partial round of a whole-march call, bit for bit.  A call of T tiles on `slots` wave slots lasts ceil(T / slots)
+// tile-times; its last T mod slots tiles keep only part of the slots busy for a whole tile-time.  Those tiles go through two
+// kernels instead (tn::launch_main_mfma, tn_render_tail_plan):
+//   field_records_kernel  a unit is (tile, segment of seg_len samples), one wave each: field_sample for its samples, and per sample
+//                         five rows of 64 floats in rec [tile][sample][5][64]: dd = (en - st) * density | r | g | b | thermal.
+//                         No compositing, nothing shared between waves: k segments per tile fill the slots k times finer.
+//   field_replay_kernel   one lane per ray of those tiles: st, en, step again from the bin edges by the same device functions, the
+//                         five recorded floats, and the statements of main_mfma_rays_kernel's compositing in sample order.  Every
+//                         operand of every operation is the whole march's, so all outputs and the depth bounds are its bits.
+// ------------------------------------------------------------------------------------------------------
+struct RecordArgs {
+    MfmaArgs m;
+    long long tile0, tiles;  // the recorded tiles [tile0, tile0 + tiles) of the call
+    int k, seg_len;          // segments per tile (none empty), samples per segment
+    float *rec;              // [tiles][S][REC_ROWS][64]
+};
+constexpr int REC_ROWS = 5;
+
+template <bool DENSE>
+__global__ void __launch_bounds__(kRaysBlock, 1) field_records_kernel(RecordArgs ra) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const MfmaArgs &a = ra.m;
+    rays_stage_blob(lds, a.blob);
+    __syncthreads();
+    const Space sp = make_space(a.space);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, h = lane >> 5;
+    const bool lin = a.lin != 0;
+    const int S = a.S;
+    float4 *c0s = reinterpret_cast<float4 *>(lds + RAYS_OFF_C0) + wave * RAYS_C0_SLOTS * 64 + lane;
+    const long long units = ra.tiles * ra.k;
+    const long long stride = (long long)gridDim.x * kRaysWaves;
+#if TN_FIELD_STAMPS
+    unsigned int stamp[kStampSlots] = {};
+#endif
+    for (long long u = (long long)blockIdx.x * kRaysWaves + wave; u < units; u += stride) {
+        const long long t = u / ra.k;
+        const long long grp = ra.tile0 + t;
+        const int s0 = (int)(u - t * ra.k) * ra.seg_len;
+        const int s1 = s0 + ra.seg_len < S ? s0 + ra.seg_len : S;
+        const long long r = grp * 64 + lane;
+        const long long rc = r < a.R ? r : a.R - 1;  // idle lanes shadow the last ray, as in the whole march
+        const float ox = a.origins[rc * 3], oy = a.origins[rc * 3 + 1], oz = a.origins[rc * 3 + 2];
+        const float dx = a.dirs[rc * 3], dy = a.dirs[rc * 3 + 1], dz = a.dirs[rc * 3 + 2];
+        const float s_near = spacing_fn(a.nears[rc], lin), s_far = spacing_fn(a.fars[rc], lin);
+        const float *tb = a.spacing + tn_ws_bin(grp * 64, 0, S) + (rc - grp * 64);
+        f32x16 c00;
+        rays_tile_bias(lds, lane, h, a.sh_shifted, dx, dy, dz, c0s, c00);
+        float en = spacing_to_eucl<true>(tb[(size_t)s0 * 64], s_near, s_far, lin);
+        float sb_next = tb[(size_t)(s0 + 1) * 64];
+        float *rec = ra.rec + ((size_t)t * S + s0) * (REC_ROWS * 64) + lane;
+        for (int i = s0; i < s1; ++i, rec += REC_ROWS * 64) {
+            float st, step, dens, cr, cg, cb, th;
+            field_sample<DENSE>(a.g, sp, lds, lane, h, c0s, c00, ox, oy, oz, dx, dy, dz, s_near, s_far, lin, tb, i, S, a.avg, en, sb_next,
+                                st, step, dens, cr, cg, cb, th TN_STAMP_ARG);
+            rec[0] = mul_rn(sub_rn(en, st), dens);
+            rec[64] = cr;
+            rec[128] = cg;
+            rec[192] = cb;
+            rec[256] = th;
+        }
+    }
+}
+
+__global__ void __launch_bounds__(256) field_replay_kernel(RecordArgs ra) {
+    const MfmaArgs &a = ra.m;
+    const long long t = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);  // one wave per tile: a wave leaves or stays as a whole
+    if (t >= ra.tiles) return;
+    const long long grp = ra.tile0 + t;
+    const int lane = threadIdx.x & 63, S = a.S;
+    const bool lin = a.lin != 0;
+    const long long r = grp * 64 + lane;
+    const bool live = r < a.R;
+    const long long rc = live ? r : a.R - 1;
+    const float s_near = spacing_fn(a.nears[rc], lin), s_far = spacing_fn(a.fars[rc], lin);
+    const float *tb = a.spacing + tn_ws_bin(grp * 64, 0, S) + (rc - grp * 64);
+    const float *rec = ra.rec + (size_t)t * S * (REC_ROWS * 64) + lane;  // (an idle lane's rows hold its shadow of the last ray)
+    // a sample's five floats and its far edge are requested PF samples before they are composited (past the end: the last sample
+    // again), so the serial walk along the ray waits for one round trip per PF samples, not per sample
+    constexpr int PF = 8;
+    float q[PF][REC_ROWS + 1];
+#pragma unroll
+    for (int p = 0; p < PF; ++p) {
+        const int j = p < S ? p : S - 1;
+#pragma unroll
+        for (int k = 0; k < REC_ROWS; ++k) q[p][k] = rec[((size_t)j * REC_ROWS + k) * 64];
+        q[p][REC_ROWS] = tb[(size_t)(j + 1) * 64];
+    }
+    float en = spacing_to_eucl<true>(tb[0], s_near, s_far, lin);
+    float accum = 0.0f, cum_w = 0.0f;
+    float wsum = 0.0f, wr = 0.0f, wg = 0.0f, wbl = 0.0f, wth = 0.0f, wsteps = 0.0f;
+    float cr = 0.0f, cg = 0.0f, cb = 0.0f, th = 0.0f, med = 0.0f, step = 0.0f;
+    float smin = INFINITY, smax = -INFINITY;
+    bool med_found = false;
+    for (int i0 = 0; i0 < S; i0 += PF) {
+#pragma unroll
+        for (int p = 0; p < PF; ++p) {
+            const int i = i0 + p;
+            if (i < S) {
+                const float dd = q[p][0];
+                cr = q[p][1]; cg = q[p][2]; cb = q[p][3]; th = q[p][4];
+                const float st = en;
+                en = spacing_to_eucl<true>(q[p][REC_ROWS], s_near, s_far, lin);
+                const int j = i + PF < S ? i + PF : S - 1;
+#pragma unroll
+                for (int k = 0; k < REC_ROWS; ++k) q[p][k] = rec[((size_t)j * REC_ROWS + k) * 64];
+                q[p][REC_ROWS] = tb[(size_t)(j + 1) * 64];
+                step = add_rn(st, en) / 2.0f;
+                const float wi = nan_to_num(mul_rn(sub_rn(1.0f, __expf(-dd)), __expf(-accum)));
+                accum += dd;
+                cum_w += wi;
+                if (!med_found && cum_w >= 0.5f) {
+                    med_found = true;
+                    med = step;
+                }
+                wsum += wi;
+                wr += mul_rn(wi, cr);
+                wg += mul_rn(wi, cg);
+                wbl += mul_rn(wi, cb);
+                wth += mul_rn(wi, th);
+                wsteps += mul_rn(wi, step);
+                smin = fminf(smin, step);
+                smax = fmaxf(smax, step);
+                if (a.out_w && live) a.out_w[r * S + i] = wi;
+            }
+        }
+    }
+    if (live) {
+        const float bg = sub_rn(1.0f, wsum);
+        const float c0 = add_rn(wr, mul_rn(cr, bg)), c1 = add_rn(wg, mul_rn(cg, bg)), c2 = add_rn(wbl, mul_rn(cb, bg));
+        const float ct = add_rn(wth, mul_rn(th, bg));
+        a.rgb[r * 3 + 0] = fminf(fmaxf(c0, 0.0f), 1.0f);
+        a.rgb[r * 3 + 1] = fminf(fmaxf(c1, 0.0f), 1.0f);
+        a.rgb[r * 3 + 2] = fminf(fmaxf(c2, 0.0f), 1.0f);
+        a.thermal[r] = fminf(fmaxf(ct, 0.0f), 1.0f);
+        a.acc[r] = wsum;
+        a.depth[r] = med_found ? med : step;
+        a.expected[r] = wsteps / add_rn(wsum, 1e-10f);
+    }
+    depth_bounds_flush(a.minmax, a.minmax.slot(grp * 64), smin, smax, lane);
 }
 
 
@@ -1226,7 +1399,7 @@ namespace tn {
 
 int launch_main_mfma(const tn_thermal_field *field, const tn_render_config *cfg, const tn_render_inputs *in,
                      const tn_render_outputs *out, long long num_rays, const float *spacing_ws, DepthSlots minmax,
-                     hipStream_t stream, int split, float *seg_scratch) {
+                     hipStream_t stream, int split, float *seg_scratch, int tail_k, float *tail_rec, int tail_slots) {
     if (!mfma_supported(field) || !field->prepared) return TN_ERR_UNSUPPORTED;
     MfmaArgs a;
     a.g = tn_make_grid(field->grid);
@@ -1275,8 +1448,37 @@ int launch_main_mfma(const tn_thermal_field *field, const tn_render_config *cfg,
         if (!(dense ? tn_ensure_dynamic_lds<main_mfma_rays_kernel<true>>(smem_rays) : tn_ensure_dynamic_lds<main_mfma_rays_kernel<false>>(smem_rays)))
             return TN_ERR_LAUNCH;
         const long long groups = (num_rays + 63) / 64;
+        // (tail_slots: the test hook of tn_render_config — a grid of fewer blocks, so that a few thousand rays are several rounds)
+        const long long cap_blocks = tail_slots > 0 ? (tail_slots + kRaysWaves - 1) / kRaysWaves : cap_rays;
+        const long long slots = cap_blocks * kRaysWaves, full = groups / slots * slots, rem = groups - full;
+        if (tail_k > 1 && tail_rec && full > 0 && rem > 0 && a.early_eps == 0.0f) {
+            // the whole rounds as ever; the last partial round as (tile, segment) records + replay (see field_records_kernel):
+            // three launches ordered by the stream alone
+            if (!(dense ? tn_ensure_dynamic_lds<field_records_kernel<true>>(smem_rays) : tn_ensure_dynamic_lds<field_records_kernel<false>>(smem_rays)))
+                return TN_ERR_LAUNCH;
+            RecordArgs ra;
+            ra.m = a;
+            ra.tile0 = full; ra.tiles = rem;
+            ra.seg_len = (a.S + tail_k - 1) / tail_k;
+            ra.k = (a.S + ra.seg_len - 1) / ra.seg_len;  // (no empty segment)
+            ra.rec = tail_rec;
+            MfmaArgs whole = a;
+            whole.R = full * 64;
+            const long long need_rec = (rem * ra.k + kRaysWaves - 1) / kRaysWaves;
+            const unsigned grid_rec = (unsigned)(need_rec < cap_blocks ? need_rec : cap_blocks);
+            if (dense) {
+                hipLaunchKernelGGL(main_mfma_rays_kernel<true>, dim3((unsigned)cap_blocks), dim3(kRaysBlock), smem_rays, stream, whole);
+                hipLaunchKernelGGL(field_records_kernel<true>, dim3(grid_rec), dim3(kRaysBlock), smem_rays, stream, ra);
+            } else {
+                hipLaunchKernelGGL(main_mfma_rays_kernel<false>, dim3((unsigned)cap_blocks), dim3(kRaysBlock), smem_rays, stream, whole);
+                hipLaunchKernelGGL(field_records_kernel<false>, dim3(grid_rec), dim3(kRaysBlock), smem_rays, stream, ra);
+            }
+            hipLaunchKernelGGL(field_replay_kernel, dim3((unsigned)((rem + 3) / 4)), dim3(256), 0, stream, ra);
+            if (hipGetLastError() != hipSuccess) return TN_ERR_LAUNCH;
+            return TN_OK;
+        }
         const long long need = (groups + kRaysWaves - 1) / kRaysWaves;
-        const unsigned grid = (unsigned)(need < cap_rays ? (need < 1 ? 1 : need) : cap_rays);
+        const unsigned grid = (unsigned)(need < cap_blocks ? (need < 1 ? 1 : need) : cap_blocks);
         if (dense)
             hipLaunchKernelGGL(main_mfma_rays_kernel<true>, dim3(grid), dim3(kRaysBlock), smem_rays, stream, a);
         else

@@ -15,7 +15,7 @@ from torch import Tensor
 
 from . import _hip
 from .samplers import linspace_bins, pdf_positions
-from .nerfacto_config.thermal_nerfacto import KERNEL_FAMILY
+from .nerfacto_config.thermal_nerfacto import KERNEL_FAMILY, tail_balance_value
 from .thermal_nerf.thermal_nerf_model import ThermalNerfModel
 
 OUTPUT_KEYS = ("rgb", "accumulation", "depth", "expected_depth", "prop_depth_0", "prop_depth_1", "thermal")
@@ -52,6 +52,8 @@ class RayRenderEngine:
         self.rc.early_stop_transmittance = float(cfg.early_termination_eps)
         self.rc.kernel_family = 0
         self.rc.initial_sampler = int(model.proposal_sampler.initial_sampler.uniform_spacing)
+        self.rc.tail_balance = tail_balance_value(getattr(cfg, "tail_balance", "auto"))
+        self._budget = int(max_workspace_bytes)
         self.fuse_chunks = bool(fuse_chunks) and self.chunk % 64 == 0
         # launches of 65 536 rays are 1024 waves — one per SIMD, half of what the field kernel needs to hide its gathers —
         # so consecutive launches go to alternating HIP streams (own workspace each) and overlap on the device
@@ -63,7 +65,8 @@ class RayRenderEngine:
         # slot's share of it holds (a longer frame: equal runs of at most that many chunks)
         self._chunks_whole = self._chunks_slot = 1
         if self.fuse_chunks:
-            per_chunk = max(self.lib.tn_render_workspace_bytes(self.rc, self.chunk), 1)
+            # (without the field pass's tail records, which are not linear in the rays and give way to the budget: _workspace_need)
+            per_chunk = max(self.lib.tn_render_workspace_bytes(self.rc, self.chunk) - self.lib.tn_render_tail_records_bytes(self.rc, self.chunk), 1)
             self._chunks_whole = max(1, int(max_workspace_bytes) // per_chunk)
             self._chunks_slot = max(1, int(max_workspace_bytes) // self.num_streams // per_chunk)
         self.launch_rays = self._chunks_slot * self.chunk  # (the largest launch of a frame that does not fit one)
@@ -74,9 +77,10 @@ class RayRenderEngine:
         self._nf_key = None
         self.timings: List[Tuple[torch.cuda.Event, torch.cuda.Event, torch.cuda.Event]] = []
 
-    def _buffers(self, dev, rays_per_launch: Optional[int] = None, launches: int = 2) -> None:
+    def _buffers(self, dev, rays_per_launch: Optional[int] = None, launches: int = 2, need: Optional[int] = None) -> None:
         rays = int(rays_per_launch or self.launch_rays)
-        need = self.lib.tn_render_workspace_bytes(self.rc, rays)
+        if need is None:
+            need = self.lib.tn_render_workspace_bytes(self.rc, rays)
         need = (need + 255) // 256 * 256
         slots = min(self.num_streams, max(launches, 1))
         if self._ws is None or self._ws.shape[1] < need or self._ws.shape[0] < slots or self._ws.device != dev:
@@ -157,6 +161,40 @@ class RayRenderEngine:
             self.rc.kernel_family, self.rc.sample_split = saved
         return prop, field, split
 
+    def _workspace_need(self, fld, pieces, frame_rays: int, sample_split: Optional[int], tail_balance) -> int:
+        """Bytes of the largest workspace the launches of ``pieces`` ask for, each under the forms it will run in (the field pass's
+        tail records depend on them: tn_render_tail_plan).  Records that would push a launch past its stream slot's share of
+        ``max_workspace_bytes`` are left out, and the library then marches that launch's last round whole: the same bits."""
+        saved = self.rc.kernel_family, self.rc.sample_split, self.rc.tail_balance
+        share = self._budget // min(self.num_streams, max(len(pieces), 1))
+        need = 0
+        try:
+            self.rc.tail_balance = self._tail_request(tail_balance)
+            for i, j in pieces:
+                _, self.rc.kernel_family, self.rc.sample_split = self._forms(fld, frame_rays, i, sample_split)
+                whole = int(self.lib.tn_render_workspace_bytes(self.rc, j - i))
+                rec = int(self.lib.tn_render_tail_records_bytes(self.rc, j - i))
+                need = max(need, whole - rec if rec and whole > share else whole)
+        finally:
+            self.rc.kernel_family, self.rc.sample_split, self.rc.tail_balance = saved
+        return need
+
+    def _tail_request(self, tail_balance) -> int:
+        """tn_render_config.tail_balance for a call: the per-call argument ("auto" | "off" | k), else the model's config.tail_balance"""
+        return tail_balance_value(getattr(self.model.config, "tail_balance", "auto") if tail_balance is None else tail_balance)
+
+    def tail_plan(self, rays: int, sample_split: Optional[int] = None, tail_balance=None) -> int:
+        """Segments per tile the library uses for the last partial round of a one-launch frame of ``rays`` rays (tn_render_tail_plan;
+        1 = whole tiles), under the forms ``render`` runs that frame in."""
+        _, _, fld = self.model._c_structs()
+        saved = self.rc.kernel_family, self.rc.sample_split, self.rc.tail_balance
+        try:
+            self.rc.tail_balance = self._tail_request(tail_balance)
+            _, self.rc.kernel_family, self.rc.sample_split = self._forms(fld, rays, 0, sample_split)
+            return int(self.lib.tn_render_tail_plan(fld, self.rc, rays))
+        finally:
+            self.rc.kernel_family, self.rc.sample_split, self.rc.tail_balance = saved
+
     def _split_request(self, sample_split: Optional[int]) -> int:
         """tn_render_config.sample_split for a call: the per-call argument, else the model's config.sample_split (0 = the library
         decides, 1 = never: the serial march's bits, as model.get_outputs honours it), else 0"""
@@ -168,22 +206,24 @@ class RayRenderEngine:
     @torch.no_grad()
     def render(self, origins: Tensor, directions: Tensor, out: Optional[Dict[str, Tensor]] = None,
                record_events: bool = False, nears: Optional[Tensor] = None, fars: Optional[Tensor] = None,
-               sample_split: Optional[int] = None) -> Dict[str, Tensor]:
+               sample_split: Optional[int] = None, tail_balance=None) -> Dict[str, Tensor]:
         """origins/directions [N,3] resident on the device -> dict of [N,C] tensors (keys = OUTPUT_KEYS).  ``nears`` / ``fars``
         [N] or [N,1]: per-ray planes already set on the bundle are honoured (NS SceneCollider.forward keeps them); absent,
         the model's NearFarCollider fills them.  ``expected_depth`` is clipped to the mid-point range of its CHUNK, exactly
         like the reference's per-chunk forward: it depends on ``chunk`` (the other outputs do not).
         ``sample_split``: segments per 64-ray tile of the field pass (tn_render_config.sample_split): None = the library's choice
         for a call of this frame's size (1 from ~500 k rays up; a small frame is marched in shorter pieces on more waves), k = that
-        many.  One value per frame, whatever launches it is cut into."""
+        many.  One value per frame, whatever launches it is cut into.  ``tail_balance``: "auto" | "off" | k for this call
+        (tn_render_config.tail_balance), None = the model's config; the outputs do not depend on it."""
         o = _hip.require_device_tensor(origins, "origins")
         d = _hip.require_device_tensor(directions, "directions")
         n, dev = o.shape[0], o.device
         pieces = self._launch_pieces(0, n, n)
-        self._buffers(dev, max((j - i for i, j in pieces), default=1), len(pieces))
+        prop0, prop1, fld = self.model._c_structs()
+        self._buffers(dev, max((j - i for i, j in pieces), default=1), len(pieces),
+                      need=self._workspace_need(fld, pieces, n, sample_split, tail_balance))
         if out is None:
             out = self.allocate_outputs(n, dev)
-        prop0, prop1, fld = self.model._c_structs()
         ins = self._inputs(dev)
         if (nears is None) != (fars is None):
             raise ValueError("pass both nears and fars, or neither")
@@ -197,6 +237,7 @@ class RayRenderEngine:
         multi = self.num_streams > 1 and len(pieces) > 1
         family = KERNEL_FAMILY[self.model.config.kernel_family]
         chunked = self.fuse_chunks and n > self.chunk
+        tail_saved, self.rc.tail_balance = self.rc.tail_balance, self._tail_request(tail_balance)
         bounds = torch.empty((-(-n // self.chunk), 2), dtype=torch.float32, device=dev) if chunked else None
         current = torch.cuda.current_stream(dev)
         if multi:
@@ -235,7 +276,7 @@ class RayRenderEngine:
             if record_events:
                 e2.record(st)
                 self.timings.append((e0, e1, e2))
-        self.rc.kernel_family, self.rc.sample_split = family, 0
+        self.rc.kernel_family, self.rc.sample_split, self.rc.tail_balance = family, 0, tail_saved
         if multi:
             for st in self._streams:
                 current.wait_stream(st)
@@ -244,7 +285,8 @@ class RayRenderEngine:
     @torch.no_grad()
     def render_shard(self, origins: Tensor, directions: Tensor, start: int, frame_rays: int,
                      out: Optional[Dict[str, Tensor]] = None, nears: Optional[Tensor] = None,
-                     fars: Optional[Tensor] = None, sample_split: Optional[int] = None) -> Tuple[Dict[str, Tensor], Tensor]:
+                     fars: Optional[Tensor] = None, sample_split: Optional[int] = None,
+                     tail_balance=None) -> Tuple[Dict[str, Tensor], Tensor]:
         """Rays [start, start + n) of a row-major frame of ``frame_rays`` rays whose reference chunking is this engine's
         ``chunk`` — a shard that need NOT begin or end on a chunk boundary, only on a multiple of 64 rays
         (distributed.render_frame_sharded_fine).  It is rendered by the launches ``render`` would use for that part of the frame,
@@ -255,7 +297,7 @@ class RayRenderEngine:
         bundle already carries (as in ``render``); absent, the collider's.  An EMPTY shard (more ranks than 64-ray tiles) is valid
         wherever it starts.  ``sample_split``: as in ``render`` — None = what the unsharded frame's launches use (1 for a frame: the
         shard, however small, then marches whole tiles); k = k segments per tile, bit-equal to ``render(frame, sample_split=k)``
-        (``shard_sample_split`` proposes the k that suits a shard's size).  Returns (outputs [n,C], bounds [chunks of the frame, 2])."""
+        (``shard_sample_split`` proposes the k that suits a shard's size).  ``tail_balance``: as in ``render``.  Returns (outputs [n,C], bounds [chunks of the frame, 2])."""
         if not self.fuse_chunks:
             raise RuntimeError("render_shard needs fuse_chunks (a chunk size that is a multiple of 64 rays)")
         o = _hip.require_device_tensor(origins, "origins")
@@ -278,8 +320,10 @@ class RayRenderEngine:
             if nears.shape[0] != n or fars.shape[0] != n:
                 raise ValueError("nears/fars must hold one value per ray of the shard")
         pieces = self._launch_pieces(start, start + n, frame_rays)
-        self._buffers(dev, max((j - i for i, j in pieces), default=1), len(pieces))
         prop0, prop1, fld = self.model._c_structs()
+        self._buffers(dev, max((j - i for i, j in pieces), default=1), len(pieces),
+                      need=self._workspace_need(fld, pieces, frame_rays, sample_split, tail_balance))
+        tail_saved, self.rc.tail_balance = self.rc.tail_balance, self._tail_request(tail_balance)
         ins = self._inputs(dev)
         ins.nears, ins.fars = self._nf[0].data_ptr(), self._nf[1].data_ptr()
         outs = _hip.tn_render_outputs()
@@ -311,7 +355,7 @@ class RayRenderEngine:
             _hip.check(self.lib.tn_field_render_chunked_fwd(fld, self.rc, ins, outs, r, ws, wsn, p0, self.chunk,
                                                             bounds.data_ptr() + 8 * (p0 // self.chunk), 0, st.cuda_stream),
                        "tn_field_render_chunked_fwd")
-        self.rc.kernel_family, self.rc.sample_split = family, 0  # (the per-launch forms above are not the engine's setting)
+        self.rc.kernel_family, self.rc.sample_split, self.rc.tail_balance = family, 0, tail_saved  # (the per-launch forms above are not the engine's setting)
         if multi:
             for st in self._streams:
                 current.wait_stream(st)

@@ -158,6 +158,10 @@ class NerfactoModelConfig:
     """Sample-split tiles of the exact-fp32 lane = ray field kernel (tn_render_config.sample_split): 0 = the library picks the
     number of segments a 64-ray tile's sample march is cut into from the call's size (1 from ~400 k rays up; a 65 536-ray chunk: 2),
     1 = never, k = k segments.  Eval only; same tolerances, other last bits than the serial march (DESIGN §7)."""
+    tail_balance: Union[Literal["auto", "off"], int] = "auto"
+    """The last partial round of tiles of a whole-march field call (tn_render_config.tail_balance): "auto" = the library evaluates
+    it as (tile, segment) records plus a replay pass where that fills the wave slots better (tn_render_tail_plan: 9 segments for
+    the 800 x 800 frame at S = 192), "off" = never, k = k segments.  Eval only; the same bits either way (DESIGN §5.2)."""
     mlp_precision: Literal["f32", "bf16x6", "f16x3"] = "f32"
     """"f32": exact fp32 MFMA (v_mfma_f32_32x32x2_f32).  Eval-only alternatives on the matrix cores' 16-bit rate, fp32 accumulate:
     "bf16x6" — every fp32 operand as three bf16 pieces (24 bits: an exact split), six piece products per fp32 product, 2^-23
@@ -180,6 +184,18 @@ class ThermalNerfactoModelConfig(NerfactoModelConfig):
 
 
 KERNEL_FAMILY = {"auto": 0, "lane_ray": 1, "ray_per_wave": 2}
+
+
+def tail_balance_value(setting) -> int:
+    """config.tail_balance as tn_render_config.tail_balance: "auto" -> 0, "off" -> 1, k -> k"""
+    if setting in (None, "auto"):
+        return 0
+    if setting == "off":
+        return 1
+    k = int(setting)
+    if k < 2:
+        raise ValueError('tail_balance is "auto", "off" or a number of segments >= 2')
+    return k
 
 
 class ThermalNerfactoModel(nn.Module):

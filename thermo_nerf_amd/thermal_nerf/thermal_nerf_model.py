@@ -22,7 +22,7 @@ from torch import Tensor, nn
 
 from .. import _hip
 from ..fields import FieldHeadNames, HashMLPDensityField
-from ..nerfacto_config.thermal_nerfacto import KERNEL_FAMILY, ThermalNerfactoModel, ThermalNerfactoModelConfig
+from ..nerfacto_config.thermal_nerfacto import KERNEL_FAMILY, tail_balance_value, ThermalNerfactoModel, ThermalNerfactoModelConfig
 from ..rays import RayBundle
 from ..rendered_image_modalities import RenderedImageModality
 from ..renderers import AccumulationRenderer, DepthRenderer, RGBRenderer
@@ -422,6 +422,7 @@ class ThermalNerfModel(ThermalNerfactoModel):
         rc.initial_sampler = int(self.proposal_sampler.initial_sampler.uniform_spacing)
         rc.sample_split = int(getattr(cfg, "sample_split", 0))
         rc.per_sample_jitter = 0 if cfg.use_single_jitter else 1
+        rc.tail_balance = tail_balance_value(getattr(cfg, "tail_balance", "auto"))
 
         ins = _hip.tn_render_inputs()
         ins.origins, ins.directions, ins.nears, ins.fars = o.data_ptr(), d.data_ptr(), nears.data_ptr(), fars.data_ptr()
