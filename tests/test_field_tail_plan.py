@@ -55,3 +55,30 @@ def test_plan_of_a_call_and_its_workspace():
     rc.tail_slots, rc.kernel_family, rc.sample_split, rc.num_nerf_samples = 16, 1, 1, 48
     assert lib.tn_render_tail_plan(fld, rc, 37 * 64) == 3 and lib.tn_render_tail_records_bytes(rc, 37 * 64) == 5 * 48 * 1280
     assert lib.tn_render_tail_plan(None, None, frame) == 1 and lib.tn_render_tail_plan(fld, rc, 0) == 1
+
+
+def test_workspace_layout_values():
+    """tn_render_workspace_bytes / tn_render_tail_records_bytes of the library before the launchers shared one layout type: the
+    literals were recorded from that build, never from the code under test."""
+    lib = _hip.load()
+    rays = (1, 63, 64, 65, 4096, 65536, 640000)
+    table = {(256, 96, 48): (104960, 104960, 104960, 207872, 6588416, 105383936, 1029122048),
+             (256, 96, 192): (141824, 141824, 141824, 281600, 8947712, 143132672, 1842096128),
+             (64, 32, 48): (39424, 39424, 39424, 76800, 2394112, 38275072, 373762048)}
+    records = {(256, 96, 192, 640000): 444334080}  # 1 808 tiles of the frame's fifth round; every other entry plans none
+    for (P0, P1, S), want in table.items():
+        rc = _hip.tn_render_config()
+        rc.num_proposal_samples[0], rc.num_proposal_samples[1], rc.num_nerf_samples = P0, P1, S
+        for R, total in zip(rays, want):
+            assert lib.tn_render_workspace_bytes(rc, R) == total, (P0, P1, S, R)
+            assert lib.tn_render_tail_records_bytes(rc, R) == records.get((P0, P1, S, R), 0), (P0, P1, S, R)
+    # tail_slots = 8: 19 tiles are two full rounds + three tiles; (workspace, records, planned segments)
+    small = {(256, 96, 48): (2141696, 184320, 2), (256, 96, 192): (3395072, 737280, 8), (64, 32, 48): (896512, 184320, 2)}
+    for (P0, P1, S), (total, rec, k) in small.items():
+        rc = _hip.tn_render_config()
+        rc.num_proposal_samples[0], rc.num_proposal_samples[1], rc.num_nerf_samples = P0, P1, S
+        rc.tail_slots, rc.kernel_family, rc.sample_split = 8, 1, 1
+        assert lib.tn_render_workspace_bytes(rc, 19 * 64) == total, (P0, P1, S)
+        assert lib.tn_render_tail_records_bytes(rc, 19 * 64) == rec, (P0, P1, S)
+        assert lib.tn_render_tail_plan(None, rc, 19 * 64) == k, (P0, P1, S)
+    assert lib.tn_render_workspace_bytes(None, 64) == 0 and lib.tn_render_workspace_bytes(rc, -1) == 0

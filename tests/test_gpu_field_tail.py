@@ -113,6 +113,39 @@ def test_the_records_are_written_and_replayed(rays, models):
     assert torch.isfinite(region).all()
 
 
+@pytest.mark.parametrize("dense", [True, False])
+def test_records_on_dense_and_on_hashed_field_grids(rays, models, dense):
+    """field_records_kernel<true> / <false>: 19 tiles on 8 slots (one block) are two full rounds plus three tiles; with the field's
+    dense re-layout and without it, the planned call gives the whole march's bits and rewrites the poisoned record region, which
+    the "off" call leaves alone (as in test_the_records_are_written_and_replayed)"""
+    model = models(48)
+    n = 8 * 64 * 2 + 3 * 64
+    o, d = rays[0][:n].contiguous(), rays[1][:n].contiguous()
+    budget = model.field.dense_budget_bytes
+    try:
+        if not dense:
+            model.field.dense_budget_bytes = 0
+            model.invalidate_prepared()
+        assert (model.field.c_struct(prepare=True).grid.num_dense_levels >= 6) == dense
+        eng = _engine(model, slots=8)
+        assert eng.tail_plan(n, tail_balance=3) == 3
+        off = _clone(eng.render(o, d, tail_balance="off"))
+        _assert_equal(eng.render(o, d, tail_balance=3), off, ("first planned call", dense))  # (sizes the workspace for the records)
+        eng.rc.kernel_family, eng.rc.sample_split, eng.rc.tail_balance = 1, 1, 3
+        whole, rec = eng.lib.tn_render_workspace_bytes(eng.rc, n), eng.lib.tn_render_tail_records_bytes(eng.rc, n)
+        eng.rc.kernel_family, eng.rc.sample_split, eng.rc.tail_balance = 0, 0, 0
+        assert rec == 3 * 48 * 5 * 64 * 4 and eng._ws.shape[1] >= whole
+        region = eng._ws[0, whole - rec:whole].view(torch.float32)
+        region.fill_(float("nan"))
+        _assert_equal(eng.render(o, d, tail_balance="off"), off, ("off", dense))
+        assert torch.isnan(region).all()
+        _assert_equal(eng.render(o, d, tail_balance=3), off, ("planned", dense))
+        assert torch.isfinite(region).all()
+    finally:
+        model.field.dense_budget_bytes = budget
+        model.invalidate_prepared()
+
+
 def test_stress_weights_reach_nan_to_num(rays, models):
     S, n = 48, TWO_ROUNDS_FIVE + 37
     eng = _engine(models(S, "stress"))

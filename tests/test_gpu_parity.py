@@ -760,6 +760,34 @@ def test_get_outputs_training_mode(impl):
                      f"spacing_starts[{i}]")
 
 
+def test_training_mode_lane_ray_on_hashed_proposal_grids():
+    """The one-launch lane = ray proposal kernel in its general (not lean) form on grids without a dense re-layout
+    (proposal_rays_kernel<0, 0, false>): a train-mode forward — jitter, per-level outputs — of 193 rays, three tiles and a lone
+    ray, with the proposal networks' dense budget at 0.  The tolerances of test_get_outputs_training_mode."""
+    gm, sd, ocfg = gpu_model("stress", 48)
+    gm.config.fused, gm.config.use_mfma = True, True
+    for net in gm.proposal_networks:
+        net.dense_budget_bytes = 0
+    gm.invalidate_prepared()
+    assert [net.c_struct().grid.num_dense_levels for net in gm.proposal_networks] == [0, 0]
+    gm.train()
+    o, d = helpers.rays(14, 14, view=3)
+    o, d = o[:193].contiguous(), d[:193].contiguous()
+    R = o.shape[0]
+    g = torch.Generator().manual_seed(17)
+    jit = [torch.rand(R, 1, generator=g) for _ in range(3)]
+    cam = torch.randint(0, 8, (R, 1), generator=g)
+    want = H.get_outputs(sd, o, d, cam, ocfg, training=True, jitter=jit)
+    with torch.no_grad():
+        got = gm._get_outputs_fused(gm.collider(bundle(o, d, cam)), jitter=torch.cat(jit, dim=1).T.contiguous().to(DEV))
+    gm.eval()
+    check_outputs(got, want, "train, lane = ray, hashed proposal grids")
+    for i in range(3):
+        assert_close(got["weights_list"][i], want["weights_list"][i], 3e-5, 1e-4, f"weights_list[{i}]")
+        assert_close(got["ray_samples_list"][i].spacing_starts, want["ray_samples_list"][i].spacing_starts, 1e-5, 0,
+                     f"spacing_starts[{i}]")
+
+
 @pytest.mark.parametrize("family", ["lane_ray", "ray_per_wave"])
 @pytest.mark.parametrize("impl", list(IMPLS))
 @pytest.mark.parametrize("S", [48, 192])

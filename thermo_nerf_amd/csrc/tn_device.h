@@ -678,9 +678,32 @@ static inline bool tn_ensure_dynamic_lds(size_t bytes) {
 namespace tn {  // host side: the entry points' argument checks and grid sizes (a null pointer is aligned)
 inline bool misaligned(const void *p, uintptr_t a) { return reinterpret_cast<uintptr_t>(p) % a != 0; }
 inline long long ceil_div(long long n, long long d) { return (n + d - 1) / d; }
+inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
+constexpr long long kCUs = 256;  // compute units of the chip: a grid-stride kernel's cap is kCUs x its resident blocks per CU
+// blocks of a grid-stride launch: one per `units_per_block` units of work, at least one, at most `max_blocks`
+inline unsigned tn_grid_blocks(long long units, long long units_per_block, long long max_blocks) {
+    const long long need = ceil_div(units, units_per_block);
+    return (unsigned)(need < max_blocks ? (need < 1 ? 1 : need) : max_blocks);
+}
 }  // namespace tn
 
 #define TN_LAUNCH_CHECK()                                  \
     do {                                                   \
         if (hipGetLastError() != hipSuccess) return TN_ERR_LAUNCH; \
     } while (0)
+
+#ifdef __HIPCC__
+// Launch KernelTrue or KernelFalse — the <true> / <false> instances of one kernel template — as a run-time bool says; the _lds
+// form first opts the chosen one in to `lds` bytes of dynamic LDS (tn_ensure_dynamic_lds) and returns false where that fails.
+template <auto KernelTrue, auto KernelFalse, typename Args>
+static inline void tn_launch_variant(bool which, unsigned grid, unsigned block, size_t lds, hipStream_t stream, const Args &args) {
+    if (which) hipLaunchKernelGGL(KernelTrue, dim3(grid), dim3(block), lds, stream, args);
+    else hipLaunchKernelGGL(KernelFalse, dim3(grid), dim3(block), lds, stream, args);
+}
+template <auto KernelTrue, auto KernelFalse, typename Args>
+static inline bool tn_launch_variant_lds(bool which, unsigned grid, unsigned block, size_t lds, hipStream_t stream, const Args &args) {
+    if (!(which ? tn_ensure_dynamic_lds<KernelTrue>(lds) : tn_ensure_dynamic_lds<KernelFalse>(lds))) return false;
+    tn_launch_variant<KernelTrue, KernelFalse>(which, grid, block, lds, stream, args);
+    return true;
+}
+#endif

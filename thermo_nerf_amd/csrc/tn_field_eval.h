@@ -302,6 +302,76 @@ inline HeadsArgs make_heads_args(const tn_thermal_field *f) {
     return a;
 }
 
+// the field's raw weights as the parameter of a prepare kernel (Raw: that file's RawField)
+template <typename Raw>
+inline Raw make_raw_field(const tn_thermal_field *f) {
+    Raw w;
+    w.b0w = f->base0.weight; w.b0b = f->base0.bias; w.b1w = f->base1.weight; w.b1b = f->base1.bias;
+    w.h0w = f->head0.weight; w.h0b = f->head0.bias; w.h1w = f->head1.weight; w.h1b = f->head1.bias;
+    w.h2w = f->head2.weight; w.h2b = f->head2.bias; w.t0w = f->th0.weight; w.t0b = f->th0.bias;
+    w.t1w = f->th1.weight; w.t1b = f->th1.bias; w.thw = f->thead.weight; w.thb = f->thead.bias;
+    w.appearance = f->appearance; w.num_images = f->num_images; w.use_avg = f->use_average_appearance;
+    return w;
+}
+
+// the members every field kernel's parameter struct has (MainArgs, MfmaArgs, H3Args, TapedArgs) ...
+template <typename Args>
+inline void fill_field_args(Args &a, const tn_thermal_field *f) {
+    a.g = tn_make_grid(f->grid);
+    a.space = f->space;
+    a.avg = f->average_init_density;
+}
+
+// ... and those of the three that render rays: the call's rays, its bin edges in the workspace and its outputs
+template <typename Args>
+inline void fill_ray_args(Args &a, const tn_thermal_field *f, const tn_render_config *cfg, const tn_render_inputs *in,
+                          const tn_render_outputs *out, long long num_rays, const float *spacing_ws, DepthSlots minmax) {
+    fill_field_args(a, f);
+    a.origins = in->origins; a.dirs = in->directions; a.nears = in->nears; a.fars = in->fars;
+    a.spacing = spacing_ws;
+    a.R = num_rays; a.S = cfg->num_nerf_samples; a.lin = cfg->initial_sampler == 1;
+    a.rgb = out->rgb; a.acc = out->accumulation; a.depth = out->depth; a.expected = out->expected_depth;
+    a.thermal = out->thermal; a.minmax = minmax;
+}
+
+// The render workspace of a call of num_rays rays, laid out once for every launcher.  Region: its byte offset, what it holds.
+//   edges         0                         final S+1 bin edges, ray-tiled (tn_ws_bin): proposal pass -> field pass
+//   minmax        the edges' bytes, rounded up to 256
+//                                           the call's expected-depth bounds as two ordered keys
+//   wk            minmax + 256              k-major copies of the two proposal MLPs
+//   scratch       minmax + kWsMid           [tiles][max(P0, P1)][64] level weights of the lane = ray proposal forms
+//   level1_edges  behind the level weights  [tiles][P1+1][64] level-1 edges of the same forms; the workspace's required part
+//                                           ends behind them, at base_bytes
+//   records       base_bytes, rounded up to 256
+//                                           the field pass's tail records (tn_render_tail_plan), records_bytes of them.  Optional:
+//                                           a caller's workspace may end at base_bytes; total_bytes (= tn_render_workspace_bytes)
+//                                           includes them only where the plan has some
+// scratch and level1_edges are dead once the edges exist: the sample-split field form keeps its records [tiles][k][SEG_ROWS][64]
+// at scratch and, at seg_cum(k), the per-sample cumulative weights [tiles][S][64] (tn_render_sample_split's cap makes them fit).
+constexpr int SEG_ROWS = 12;  // optical depth | sum w | sum w r,g,b | sum w th | sum w step | last sample's r,g,b,th | last mid-point
+struct RenderWorkspace {
+    static constexpr size_t kWsMid = 2048;
+    size_t tiles, minmax, wk, scratch, level1_edges, base_bytes, records, records_bytes, total_bytes;
+    RenderWorkspace(const tn_render_config *cfg, int64_t num_rays) {
+        const size_t P0 = (size_t)cfg->num_proposal_samples[0], P1 = (size_t)cfg->num_proposal_samples[1];
+        tiles = (size_t)((num_rays + 63) >> 6);
+        const size_t nmax = P0 > P1 ? P0 : P1;
+        minmax = align_up(tn_ws_bin_floats(num_rays, cfg->num_nerf_samples) * sizeof(float), 256);
+        wk = minmax + 256;
+        scratch = minmax + kWsMid;
+        level1_edges = scratch + tiles * 64 * nmax * sizeof(float);
+        base_bytes = level1_edges + tiles * 64 * (P1 + 1) * sizeof(float);
+        records = align_up(base_bytes, 256);
+        records_bytes = tn_render_tail_records_bytes(cfg, num_rays);
+        total_bytes = records_bytes ? records + records_bytes : base_bytes;
+    }
+    size_t seg_cum(int k) const { return scratch + tiles * (size_t)k * SEG_ROWS * 64 * sizeof(float); }
+    template <typename T = float>
+    static T *at(const void *workspace, size_t offset) {
+        return reinterpret_cast<T *>(reinterpret_cast<char *>(const_cast<void *>(workspace)) + offset);
+    }
+};
+
 }  // namespace tn
 
 static inline int tn_check_linear(const tn_linear &l, int in_dim, int out_dim) {

@@ -40,8 +40,8 @@ using namespace tn;
 namespace tn {
 // implemented in tn_render_mfma.hip
 int launch_main_mfma(const tn_thermal_field *field, const tn_render_config *cfg, const tn_render_inputs *in,
-                     const tn_render_outputs *out, long long num_rays, const float *spacing_ws, DepthSlots minmax,
-                     hipStream_t stream, int split, float *seg_scratch, int tail_k, float *tail_rec, int tail_slots);
+                     const tn_render_outputs *out, long long num_rays, const RenderWorkspace &ws, void *workspace, DepthSlots minmax,
+                     hipStream_t stream, int split, int tail_k);
 // implemented in tn_render_h3.hip (the two split-precision policies of one kernel)
 int launch_main_b6(const tn_thermal_field *field, const tn_render_config *cfg, const tn_render_inputs *in,
                    const tn_render_outputs *out, long long num_rays, const float *spacing_ws, DepthSlots minmax,
@@ -56,7 +56,6 @@ namespace {
 constexpr int kBlock = 256;
 constexpr int kWaves = kBlock / TN_WAVE;
 constexpr int PH = 16;  // proposal-net hidden width (proposal_net_args_list: hidden_dim 16)
-constexpr size_t kWsMid = 2048;      // workspace bytes between the final edges and the proposal scratch
 constexpr int kPropWFloats = 208;    // per net: W0 k-major [10][16] | b0 [16] | w1 [16] | b1 [1] (+ pad)
 
 struct PropNet {
@@ -189,6 +188,7 @@ __device__ __forceinline__ void store_bins(const float *bins, int nb, float s_ne
 // kernel is latency-bound and wants every ray of a training batch resident at once.  At the 176 VGPRs hipcc takes when left
 // alone, 2 waves fit a SIMD and a 4096-ray batch runs as two rounds (101 us); capped at 128 (42 spilled dwords, L1-resident
 // scratch) all 4096 waves are resident: 85 us.
+constexpr long long kPropMaxBlocks = kCUs * 8;
 __global__ void __launch_bounds__(kBlock, 4) proposal_kernel(PropArgs a, int nmax, int nbmax) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int in0 = 2 * a.net[0].g.num_levels, in1 = 2 * a.net[1].g.num_levels;
@@ -430,6 +430,7 @@ __device__ __forceinline__ void pdf_walk(const float *w, int n_in, float total, 
 // LEAN = the eval default as compile-time facts (no jitter, piecewise spacing, anneal 1, scene contraction, both nets the
 // 5-level / 16-hidden shape, no per-level outputs): the run-time switches of the general form cost scalar registers
 // (spilled to lanes and read back per sample) and branches inside the sample loops.
+constexpr long long kPropRaysMaxBlocks = kCUs * TN_PROP_WAVES;  // TN_PROP_WAVES workgroups (x 4 waves) per CU; the segment kernels too
 template <int ND0, int ND1, bool LEAN>
 __global__ void __launch_bounds__(kBlock, TN_PROP_WAVES) proposal_rays_kernel(PropRaysArgs ra) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -717,6 +718,7 @@ struct MainArgs {
 
 constexpr int GF = 15;  // geo_feat_dim supported by the fused path
 
+constexpr long long kMainValuMaxBlocks = kCUs * 2;
 __global__ void __launch_bounds__(kBlock) main_valu_kernel(MainArgs a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int in_dim = 2 * a.g.num_levels;
@@ -851,8 +853,6 @@ __global__ void depth_clip_chunked_kernel(float *__restrict__ expected, long lon
     expected[r] = fminf(fmaxf(expected[r], bounds[2 * slot]), bounds[2 * slot + 1]);
 }
 
-inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
-
 inline PropNet make_prop(const tn_density_field *f) {
     PropNet p;
     p.g = tn_make_grid(f->grid);
@@ -862,32 +862,12 @@ inline PropNet make_prop(const tn_density_field *f) {
     return p;
 }
 
-inline unsigned ray_grid(long long R, int blocks_per_cu) {
-    const long long need = (R + kWaves - 1) / kWaves;
-    const long long cap = 256LL * blocks_per_cu;
-    return (unsigned)(need < cap ? (need < 1 ? 1 : need) : cap);
-}
-
 }  // namespace
 
 extern "C" {
 
-static size_t render_workspace_base_bytes(const tn_render_config *cfg, int64_t num_rays) {
-    if (!cfg || num_rays < 0) return 0;
-    // [final edges, ray-tiled] [kWsMid B: depth min/max (8 B) | at +256: the proposal MLPs' k-major weight copies]
-    // [proposal scratch: level weights + level-1 edges, ray-tiled]
-    const size_t tiles = (size_t)((num_rays + 63) >> 6);
-    const int P0 = cfg->num_proposal_samples[0], P1 = cfg->num_proposal_samples[1];
-    const size_t nmax = (size_t)(P0 > P1 ? P0 : P1);
-    return align_up(tn_ws_bin_floats(num_rays, cfg->num_nerf_samples) * sizeof(float), 256) + kWsMid +
-           tiles * 64 * (nmax + (size_t)P1 + 1) * sizeof(float);
-}
-
-// ... [the records of the field pass's last partial round (tn_render_tail_plan), 256-byte aligned]
 size_t tn_render_workspace_bytes(const tn_render_config *cfg, int64_t num_rays) {
-    if (!cfg || num_rays < 0) return 0;
-    const size_t rec = tn_render_tail_records_bytes(cfg, num_rays);
-    return rec ? align_up(render_workspace_base_bytes(cfg, num_rays), 256) + rec : render_workspace_base_bytes(cfg, num_rays);
+    return !cfg || num_rays < 0 ? 0 : RenderWorkspace(cfg, num_rays).total_bytes;
 }
 
 static int check_render_common(const tn_render_config *cfg, int64_t num_rays, void *workspace, size_t workspace_bytes) {
@@ -895,13 +875,8 @@ static int check_render_common(const tn_render_config *cfg, int64_t num_rays, vo
     const int P0 = cfg->num_proposal_samples[0], P1 = cfg->num_proposal_samples[1], S = cfg->num_nerf_samples;
     if (P0 < 1 || P1 < 1 || S < 1 || P0 > 1024 || P1 > 1024 || S > 1024 || num_rays < 0) return TN_ERR_SHAPE;
     if (cfg->initial_sampler != 0 && cfg->initial_sampler != 1) return TN_ERR_UNSUPPORTED;
-    if (workspace_bytes < render_workspace_base_bytes(cfg, num_rays)) return TN_ERR_WORKSPACE;  // (the tail records are optional)
+    if (workspace_bytes < RenderWorkspace(cfg, num_rays).base_bytes) return TN_ERR_WORKSPACE;  // (the tail records are optional)
     return TN_OK;
-}
-
-static inline unsigned *ws_minmax(void *workspace, int64_t num_rays, int S) {
-    return reinterpret_cast<unsigned *>(reinterpret_cast<char *>(workspace) +
-                                        align_up(tn_ws_bin_floats(num_rays, S) * sizeof(float), 256));
 }
 
 int tn_proposal_sample_fwd(const tn_density_field *prop0, const tn_density_field *prop1, const tn_render_config *cfg,
@@ -917,6 +892,7 @@ int tn_proposal_sample_fwd(const tn_density_field *prop0, const tn_density_field
     if (prop0->l0.out_dim != PH || prop1->l0.out_dim != PH) return TN_ERR_UNSUPPORTED;
     const int P0 = cfg->num_proposal_samples[0], P1 = cfg->num_proposal_samples[1], S = cfg->num_nerf_samples;
     hipStream_t s = (hipStream_t)stream;
+    const RenderWorkspace ws(cfg, num_rays);
     PropArgs pa;
     pa.net[0] = make_prop(prop0);
     pa.net[1] = make_prop(prop1);
@@ -926,7 +902,7 @@ int tn_proposal_sample_fwd(const tn_density_field *prop0, const tn_density_field
     pa.jper = cfg->per_sample_jitter != 0;
     pa.R = num_rays; pa.P0 = P0; pa.P1 = P1; pa.S = S; pa.training = cfg->training; pa.anneal = cfg->pdf_anneal;
     pa.lin = cfg->initial_sampler == 1;
-    pa.ws_spacing = reinterpret_cast<float *>(workspace);
+    pa.ws_spacing = ws.at(workspace, 0);
     for (int i = 0; i < 3; ++i) { pa.out_spacing[i] = out->spacing_bins[i]; pa.out_eucl[i] = out->eucl_bins[i]; }
     pa.out_w[0] = out->weights[0]; pa.out_w[1] = out->weights[1];
     pa.prop_depth[0] = out->prop_depth_0; pa.prop_depth[1] = out->prop_depth_1;
@@ -937,31 +913,25 @@ int tn_proposal_sample_fwd(const tn_density_field *prop0, const tn_density_field
                                       two_layer_floats(2 * prop1->grid.num_levels, PH, 1) +
                                       kWaves * (3 * nbmax + nmax)) * sizeof(float);
 
+    // k-major weight copies for the scalar-operand MLP of both kernel forms (two tiny blocks, same stream)
+    float *wk = ws.at(workspace, ws.wk);
+    hipLaunchKernelGGL(prop_weights_kmajor_kernel, dim3(2), dim3(256), 0, s, pa.net[0], pa.net[1], wk, ws.at<unsigned>(workspace, ws.minmax));
+    pa.wk = wk;
     // lane = ray needs >= ~1250 tiles to fill the chip (a tile marches its 64 rays serially: 1.1 ms whatever the count);
     // below ~80 k rays one wave per ray finishes sooner (4096 rays: 0.08 vs 1.1 ms).  cfg->kernel_family forces either form.
-    {   // k-major weight copies for the scalar-operand MLP of both kernel forms (two tiny blocks, same stream)
-        float *wk = reinterpret_cast<float *>(reinterpret_cast<char *>(workspace) +
-                                              align_up(tn_ws_bin_floats(num_rays, S) * sizeof(float), 256) + 256);
-        hipLaunchKernelGGL(prop_weights_kmajor_kernel, dim3(2), dim3(256), 0, s, pa.net[0], pa.net[1], wk,
-                           ws_minmax(workspace, num_rays, S));
-        pa.wk = wk;
-    }
     const bool small_call = tn_render_kernel_form(nullptr, cfg, num_rays, 0) == 2;
     if (!small_call) {
         // lane = ray
         PropRaysArgs ra;
         ra.p = pa;
         ra.nmax = nmax;
-        char *scratch = reinterpret_cast<char *>(workspace) + align_up(tn_ws_bin_floats(num_rays, S) * sizeof(float), 256) + kWsMid;
-        const size_t tiles = (size_t)((num_rays + 63) >> 6);
-        ra.w_scratch = reinterpret_cast<float *>(scratch);
-        ra.b1_scratch = ra.w_scratch + tiles * 64 * (size_t)nmax;
+        const long long tiles = (long long)ws.tiles;
+        ra.w_scratch = ws.at(workspace, ws.scratch);
+        ra.b1_scratch = ws.at(workspace, ws.level1_edges);
         const size_t rsmem = (size_t)(two_layer_floats(2 * prop0->grid.num_levels, PH, 1) +
                                       two_layer_floats(2 * prop1->grid.num_levels, PH, 1) + (P0 + 1) + (P1 + 1) + (S + 1)) *
                              sizeof(float);
-        const long long need = ((long long)tiles + kWaves - 1) / kWaves;
-        constexpr long long kMaxGrid = 256LL * TN_PROP_WAVES;  // TN_PROP_WAVES workgroups (x 4 waves) per CU
-        const unsigned grid = (unsigned)(need < kMaxGrid ? (need < 1 ? 1 : need) : kMaxGrid);
+        auto blocks = [](long long units) { return tn_grid_blocks(units, kWaves, kPropRaysMaxBlocks); };
         const int nd0 = pa.net[0].g.num_dense, nd1 = pa.net[1].g.num_dense;
         const bool five = pa.net[0].g.num_levels == 5 && pa.net[1].g.num_levels == 5;
         bool lean = five && !pa.jitter && !pa.lin && pa.anneal == 1.0f && pa.net[0].space.contraction && pa.net[1].space.contraction &&
@@ -970,53 +940,41 @@ int tn_proposal_sample_fwd(const tn_density_field *prop0, const tn_density_field
         // calls that leave most wave slots idle: density evaluations as (tile, segment) virtual tiles, scans + PDF walks per tile — the
         // same edges bit for bit (see proposal_density_segments_kernel).  Measured (tools/ab_prop_split.sh, S = 48, one-launch form ->
         // segments): 65 536 rays 0.62 -> 0.41 ms, 80 000: 0.73 -> 0.44, 160 000: 0.92 -> 0.80, 259 200: 1.16 -> 1.27: up to 3 072 tiles
-        constexpr long long kSlots = 256LL * TN_PROP_WAVES * kWaves;
-        if (TN_PROP_SPLIT && lean && five && 4 * (long long)tiles < 3 * kSlots && ((nd0 == 5 && nd1 == 4) || (nd0 == 0 && nd1 == 0)) && P0 >= 64 &&
+        constexpr long long kSlots = kPropRaysMaxBlocks * kWaves;
+        if (TN_PROP_SPLIT && lean && five && 4 * tiles < 3 * kSlots && ((nd0 == 5 && nd1 == 4) || (nd0 == 0 && nd1 == 0)) && P0 >= 64 &&
             P1 >= 32) {
             PropSplitArgs sa;
             sa.ra = ra;
             const int counts[2] = {P0, P1}, kcap[2] = {8, 4};
             for (int l = 0; l < 2; ++l) {
-                long long k = (3 * kSlots + (long long)tiles - 1) / (long long)tiles;  // ~three rounds of virtual tiles
+                long long k = (3 * kSlots + tiles - 1) / tiles;  // ~three rounds of virtual tiles
                 if (k > kcap[l]) k = kcap[l];
                 if (k < 1) k = 1;
                 sa.len[l] = (int)((counts[l] + k - 1) / k);
                 sa.k[l] = (counts[l] + sa.len[l] - 1) / sa.len[l];
             }
-            auto blocks = [&](long long units) {
-                const long long nb = (units + kWaves - 1) / kWaves;
-                return dim3((unsigned)(nb < kMaxGrid ? (nb < 1 ? 1 : nb) : kMaxGrid));
-            };
             const size_t lds0 = (size_t)(P0 + 1) * sizeof(float);
             const size_t ldsr0 = (size_t)(P0 + 1 + P1 + 1) * sizeof(float), ldsr1 = (size_t)(P0 + 1 + S + 1) * sizeof(float);
-            if (nd0 == 5) {
-                hipLaunchKernelGGL((proposal_density_segments_kernel<5, 0>), blocks((long long)tiles * sa.k[0]), dim3(kBlock), lds0, s, sa);
-                hipLaunchKernelGGL(proposal_resample_kernel<0>, blocks((long long)tiles), dim3(kBlock), ldsr0, s, sa);
-                hipLaunchKernelGGL((proposal_density_segments_kernel<4, 1>), blocks((long long)tiles * sa.k[1]), dim3(kBlock), 0, s, sa);
-            } else {
-                hipLaunchKernelGGL((proposal_density_segments_kernel<0, 0>), blocks((long long)tiles * sa.k[0]), dim3(kBlock), lds0, s, sa);
-                hipLaunchKernelGGL(proposal_resample_kernel<0>, blocks((long long)tiles), dim3(kBlock), ldsr0, s, sa);
-                hipLaunchKernelGGL((proposal_density_segments_kernel<0, 1>), blocks((long long)tiles * sa.k[1]), dim3(kBlock), 0, s, sa);
-            }
-            hipLaunchKernelGGL(proposal_resample_kernel<1>, blocks((long long)tiles), dim3(kBlock), ldsr1, s, sa);
+            tn_launch_variant<proposal_density_segments_kernel<5, 0>, proposal_density_segments_kernel<0, 0>>(
+                nd0 == 5, blocks(tiles * sa.k[0]), kBlock, lds0, s, sa);
+            hipLaunchKernelGGL(proposal_resample_kernel<0>, dim3(blocks(tiles)), dim3(kBlock), ldsr0, s, sa);
+            tn_launch_variant<proposal_density_segments_kernel<4, 1>, proposal_density_segments_kernel<0, 1>>(
+                nd0 == 5, blocks(tiles * sa.k[1]), kBlock, 0, s, sa);
+            hipLaunchKernelGGL(proposal_resample_kernel<1>, dim3(blocks(tiles)), dim3(kBlock), ldsr1, s, sa);
             TN_LAUNCH_CHECK();
             return TN_OK;
         }
-        if (five && nd0 == 5 && nd1 == 4 && lean)
-            hipLaunchKernelGGL((proposal_rays_kernel<5, 4, true>), dim3(grid), dim3(kBlock), rsmem, s, ra);
-        else if (five && nd0 == 5 && nd1 == 4)
-            hipLaunchKernelGGL((proposal_rays_kernel<5, 4, false>), dim3(grid), dim3(kBlock), rsmem, s, ra);
-        else if (nd0 == 0 && nd1 == 0 && lean)
-            hipLaunchKernelGGL((proposal_rays_kernel<0, 0, true>), dim3(grid), dim3(kBlock), rsmem, s, ra);
+        if (five && nd0 == 5 && nd1 == 4)
+            tn_launch_variant<proposal_rays_kernel<5, 4, true>, proposal_rays_kernel<5, 4, false>>(lean, blocks(tiles), kBlock, rsmem, s, ra);
         else if (nd0 == 0 && nd1 == 0)
-            hipLaunchKernelGGL((proposal_rays_kernel<0, 0, false>), dim3(grid), dim3(kBlock), rsmem, s, ra);
+            tn_launch_variant<proposal_rays_kernel<0, 0, true>, proposal_rays_kernel<0, 0, false>>(lean, blocks(tiles), kBlock, rsmem, s, ra);
         else
-            hipLaunchKernelGGL((proposal_rays_kernel<-1, -1, false>), dim3(grid), dim3(kBlock), rsmem, s, ra);
+            hipLaunchKernelGGL((proposal_rays_kernel<-1, -1, false>), dim3(blocks(tiles)), dim3(kBlock), rsmem, s, ra);
         TN_LAUNCH_CHECK();
         return TN_OK;
     }
     if (prop_smem > 64 * 1024 && !tn_ensure_dynamic_lds<proposal_kernel>(prop_smem)) return TN_ERR_LAUNCH;
-    hipLaunchKernelGGL(proposal_kernel, dim3(ray_grid(num_rays, 8)), dim3(kBlock), prop_smem, s, pa, nmax, nbmax);
+    hipLaunchKernelGGL(proposal_kernel, dim3(tn_grid_blocks(num_rays, kWaves, kPropMaxBlocks)), dim3(kBlock), prop_smem, s, pa, nmax, nbmax);
     TN_LAUNCH_CHECK();
     return TN_OK;
 }
@@ -1034,10 +992,10 @@ static int field_render_fwd(const tn_thermal_field *field, const tn_render_confi
     if (cfg->training && !in->camera_indices) return TN_ERR_NULL;
     TN_TRY(tn_check_thermal_field(field));
     if (field->geo_feat_dim != GF) return TN_ERR_UNSUPPORTED;
-    const int S = cfg->num_nerf_samples;
     hipStream_t s = (hipStream_t)stream;
-    const float *ws_spacing = reinterpret_cast<const float *>(workspace);
-    DepthSlots minmax{ws_minmax(workspace, num_rays, S), 0, 0};
+    const RenderWorkspace ws(cfg, num_rays);
+    const float *ws_spacing = ws.at(workspace, 0);
+    DepthSlots minmax{ws.at<unsigned>(workspace, ws.minmax), 0, 0};
     int slots = 1;
     if (depth_bounds) {
         if (chunk_rays < 64 || chunk_rays % 64 != 0 || first_ray < 0 || first_ray % 64 != 0) return TN_ERR_UNSUPPORTED;
@@ -1057,36 +1015,22 @@ static int field_render_fwd(const tn_thermal_field *field, const tn_render_confi
     } else if (field->prepared_f16x3 && split_ok) {
         TN_TRY(launch_main_h3(field, cfg, in, out, (long long)num_rays, ws_spacing, minmax, s));
     } else if (field->prepared) {
-        // sample-split tiles (tn_render_sample_split): records + per-sample cumulative weights live in the proposal pass's scratch
-        // region of this workspace (dead once the bin edges exist; 12 k + S floats per ray <= its 256 + 97 by the policy's cap)
+        // sample-split tiles (tn_render_sample_split), or the last partial round as records + replay (tn_render_tail_plan) where the
+        // caller's workspace reaches that far
         const int split = out->weights[2] ? 1 : tn_render_sample_split(field, cfg, num_rays);
-        float *seg_scratch = reinterpret_cast<float *>(reinterpret_cast<char *>(workspace) +
-                                                       align_up(tn_ws_bin_floats(num_rays, S) * sizeof(float), 256) + kWsMid);
-        // the last partial round as records + replay (tn_render_tail_plan), where the caller's workspace reaches that far
         int tail_k = tn_render_tail_plan(field, cfg, num_rays);
-        const size_t rec_off = align_up(render_workspace_base_bytes(cfg, num_rays), 256);
-        const size_t rec_bytes = tn_render_tail_records_bytes(cfg, num_rays);
-        if (out->weights[2] || rec_bytes == 0 || workspace_bytes < rec_off + rec_bytes) tail_k = 1;
-        float *tail_rec = reinterpret_cast<float *>(reinterpret_cast<char *>(workspace) + rec_off);
-        TN_TRY(launch_main_mfma(field, cfg, in, out, (long long)num_rays, ws_spacing, minmax, s, split, seg_scratch, tail_k, tail_rec,
-                                cfg->tail_slots));
+        if (out->weights[2] || ws.records_bytes == 0 || workspace_bytes < ws.records + ws.records_bytes) tail_k = 1;
+        TN_TRY(launch_main_mfma(field, cfg, in, out, (long long)num_rays, ws, workspace, minmax, s, split, tail_k));
     } else {
         MainArgs ma;
-        ma.g = tn_make_grid(field->grid);
-        ma.space = field->space;
+        fill_ray_args(ma, field, cfg, in, out, num_rays, ws_spacing, minmax);
         ma.b0w = field->base0.weight; ma.b0b = field->base0.bias; ma.b1w = field->base1.weight; ma.b1b = field->base1.bias;
         ma.heads = make_heads_args(field);
-        ma.avg = field->average_init_density;
-        ma.origins = in->origins; ma.dirs = in->directions; ma.nears = in->nears; ma.fars = in->fars;
-        ma.cam = in->camera_indices;
-        ma.spacing = ws_spacing;
-        ma.R = num_rays; ma.S = S; ma.training = cfg->training; ma.lin = cfg->initial_sampler == 1;
-        ma.rgb = out->rgb; ma.acc = out->accumulation; ma.depth = out->depth; ma.expected = out->expected_depth;
-        ma.thermal = out->thermal; ma.out_w = out->weights[2]; ma.minmax = minmax;
+        ma.cam = in->camera_indices; ma.training = cfg->training; ma.out_w = out->weights[2];
         const size_t main_smem = (size_t)(two_layer_floats(2 * field->grid.num_levels, HW, 1 + GF) +
                                           heads_floats(GF, field->app_dim)) * sizeof(float);
         if (!tn_ensure_dynamic_lds<main_valu_kernel>(main_smem)) return TN_ERR_LAUNCH;
-        hipLaunchKernelGGL(main_valu_kernel, dim3(ray_grid(num_rays, 2)), dim3(kBlock), main_smem, s, ma);
+        hipLaunchKernelGGL(main_valu_kernel, dim3(tn_grid_blocks(num_rays, kWaves, kMainValuMaxBlocks)), dim3(kBlock), main_smem, s, ma);
         TN_LAUNCH_CHECK();
     }
     if (depth_bounds) {

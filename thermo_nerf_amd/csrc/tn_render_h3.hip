@@ -40,6 +40,7 @@ constexpr int LG = 4;
 // and piece.  F16x3: 64 KB, two 256-thread blocks per CU; BF16x6: 96 KB, ONE 512-thread block per CU (both: two waves per SIMD).
 struct F16x3 {
     static constexpr int NP = 2, kBlock = 256, kBlocksPerCU = 2;
+    static constexpr long long kMaxBlocks = kCUs * kBlocksPerCU;
     static constexpr bool kShInLds = false;  // SH(dir) operand of a tile's rays: 16 VGPRs held over the sample loop
     typedef _Float16 elem;
     typedef v8h vec;
@@ -69,6 +70,7 @@ struct F16x3 {
 };
 struct BF16x6 {
     static constexpr int NP = 3, kBlock = 512, kBlocksPerCU = 1;
+    static constexpr long long kMaxBlocks = kCUs * kBlocksPerCU;
     // SH(dir) operand of a tile's rays (24 VGPRs, constant over the sample loop) parked in LDS: 6 KB per wave behind the blob
     static constexpr bool kShInLds = true;
     typedef __bf16 elem;
@@ -692,26 +694,16 @@ static int launch_main_split(const tn_thermal_field *field, const float *blob, c
                              hipStream_t stream) {
     if (!h3_supported(field) || !blob || cfg->training) return TN_ERR_UNSUPPORTED;
     H3Args a;
-    a.g = tn_make_grid(field->grid);
-    a.space = field->space;
+    fill_ray_args(a, field, cfg, in, out, num_rays, spacing_ws, minmax);
     a.blob = blob;
-    a.avg = field->average_init_density;
     a.sh_shifted = field->sh_shifted;
-    a.origins = in->origins; a.dirs = in->directions; a.nears = in->nears; a.fars = in->fars;
-    a.spacing = spacing_ws;
-    a.R = num_rays; a.S = cfg->num_nerf_samples; a.lin = cfg->initial_sampler == 1;
-    a.rgb = out->rgb; a.acc = out->accumulation; a.depth = out->depth; a.expected = out->expected_depth;
-    a.thermal = out->thermal; a.minmax = minmax;
     a.early_eps = fminf(fmaxf(cfg->early_stop_transmittance, 0.0f), 0.25f);
     constexpr int kWaves = P::kBlock / TN_WAVE;
     const size_t smem = (size_t)Lay<P::NP>::BLOB_FLOATS * sizeof(float) + (P::kShInLds ? (size_t)kWaves * 64 * 2 * P::NP * 16 : 0);
     if (!tn_ensure_dynamic_lds<main_split_rays_kernel<P>>(smem)) return TN_ERR_LAUNCH;
-    const long long groups = (num_rays + 63) / 64;
-    const long long need = (groups + kWaves - 1) / kWaves;
-    const long long cap = 256LL * P::kBlocksPerCU;
-    const unsigned grid = (unsigned)(need < cap ? (need < 1 ? 1 : need) : cap);
-    hipLaunchKernelGGL(main_split_rays_kernel<P>, dim3(grid), dim3(P::kBlock), smem, stream, a);
-    if (hipGetLastError() != hipSuccess) return TN_ERR_LAUNCH;
+    hipLaunchKernelGGL(main_split_rays_kernel<P>, dim3(tn_grid_blocks((num_rays + 63) / 64, kWaves, P::kMaxBlocks)), dim3(P::kBlock),
+                       smem, stream, a);
+    TN_LAUNCH_CHECK();
     return TN_OK;
 }
 
@@ -734,16 +726,10 @@ static int field_prepare_split(const tn_thermal_field *f, void *prepared_dev, si
     TN_TRY(tn_check_thermal_field(f));
     if (!h3_supported(f)) return TN_ERR_UNSUPPORTED;
     if (bytes < (size_t)LY::BLOB_FLOATS * sizeof(float)) return TN_ERR_WORKSPACE;
-    RawField w;
-    w.b0w = f->base0.weight; w.b0b = f->base0.bias; w.b1w = f->base1.weight; w.b1b = f->base1.bias;
-    w.h0w = f->head0.weight; w.h0b = f->head0.bias; w.h1w = f->head1.weight; w.h1b = f->head1.bias;
-    w.h2w = f->head2.weight; w.h2b = f->head2.bias; w.t0w = f->th0.weight; w.t0b = f->th0.bias;
-    w.t1w = f->th1.weight; w.t1b = f->th1.bias; w.thw = f->thead.weight; w.thb = f->thead.bias;
-    w.appearance = f->appearance; w.num_images = f->num_images; w.use_avg = f->use_average_appearance;
     const int threads = N_COMBOS * 64 * 8 + (LY::BLOB_FLOATS - LY::A_FLOATS);
-    hipLaunchKernelGGL(field_prepare_split_kernel<P>, dim3((threads + 255) / 256), dim3(256), 0, (hipStream_t)stream, w,
-                       reinterpret_cast<float *>(prepared_dev));
-    if (hipGetLastError() != hipSuccess) return TN_ERR_LAUNCH;
+    hipLaunchKernelGGL(field_prepare_split_kernel<P>, dim3((threads + 255) / 256), dim3(256), 0, (hipStream_t)stream,
+                       make_raw_field<RawField>(f), reinterpret_cast<float *>(prepared_dev));
+    TN_LAUNCH_CHECK();
     return TN_OK;
 }
 
@@ -775,14 +761,14 @@ int tn_bf16x6_split_product(const float *a, const float *b, int64_t n, float *pi
     if (n < 0) return TN_ERR_SHAPE;
     hipLaunchKernelGGL(bf16x6_split_product_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a, b,
                        (long long)n, pieces_a, pieces_b, out);
-    if (hipGetLastError() != hipSuccess) return TN_ERR_LAUNCH;
+    TN_LAUNCH_CHECK();
     return TN_OK;
 }
 
 int tn_bf16_mfma_value_probe(float a_value, float b_value, float *out, void *stream) {
     if (!out) return TN_ERR_NULL;
     hipLaunchKernelGGL(bf16_mfma_value_probe_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, a_value, b_value, out);
-    if (hipGetLastError() != hipSuccess) return TN_ERR_LAUNCH;
+    TN_LAUNCH_CHECK();
     return TN_OK;
 }
 

@@ -210,7 +210,6 @@ struct MfmaArgs {
     int split, seg_len;
     float *seg_rec, *seg_cum;
 };
-constexpr int SEG_ROWS = 12;  // optical depth | sum w | sum w r,g,b | sum w th | sum w step | last sample's r,g,b,th | last mid-point
 
 #define MFMA32(acc, a, b) acc = __builtin_amdgcn_mfma_f32_32x32x2f32((a), (b), (acc), 0, 0, 0)
 #define MFMA16(acc, a, b) acc = __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (acc), 0, 0, 0)
@@ -387,6 +386,7 @@ __device__ __forceinline__ float combine_halves(float2 p) {
 }
 
 
+constexpr long long kMainMfmaMaxBlocks = kCUs * 2;  // 2 resident blocks per CU (LDS 77 KB each)
 __global__ void __launch_bounds__(kBlock, 2) main_mfma_kernel(MfmaArgs a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     {   // stage the prepared blob (float4, coalesced)
@@ -803,6 +803,7 @@ __device__ __forceinline__ void field_sample(const Grid &g_, const Space &sp, co
     cr = nan_to_num(cr); cg = nan_to_num(cg); cb = nan_to_num(cb); th = nan_to_num(th);  // eval renderers
 }
 
+constexpr long long kRaysMaxBlocks = kCUs;  // 1 resident block of 8 waves per CU (LDS 155 KB); field_records_kernel the same
 template <bool DENSE, bool SPLIT = false>
 __global__ void __launch_bounds__(kRaysBlock, 1) main_mfma_rays_kernel(MfmaArgs a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -1177,6 +1178,7 @@ __device__ __forceinline__ void tape_store(float *dst, long long row0, long long
 // gathers a wave has more memory operations outstanding than the 6-bit counter holds; two levels per group: 429 -> 413 us at S=192
 #define TN_TRAIN_JAC_LG 2
 #endif
+constexpr long long kTapedMaxBlocks = kCUs * 2;
 template <bool TAPE, bool JAC = false>
 __global__ void __launch_bounds__(kBlock, 2) field_fwd_taped_kernel(TapedArgs a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -1398,99 +1400,69 @@ inline bool mfma_supported(const tn_thermal_field *f) {
 namespace tn {
 
 int launch_main_mfma(const tn_thermal_field *field, const tn_render_config *cfg, const tn_render_inputs *in,
-                     const tn_render_outputs *out, long long num_rays, const float *spacing_ws, DepthSlots minmax,
-                     hipStream_t stream, int split, float *seg_scratch, int tail_k, float *tail_rec, int tail_slots) {
+                     const tn_render_outputs *out, long long num_rays, const RenderWorkspace &ws, void *workspace, DepthSlots minmax,
+                     hipStream_t stream, int split, int tail_k) {
     if (!mfma_supported(field) || !field->prepared) return TN_ERR_UNSUPPORTED;
     MfmaArgs a;
-    a.g = tn_make_grid(field->grid);
-    a.space = field->space;
+    fill_ray_args(a, field, cfg, in, out, num_rays, ws.at(workspace, 0), minmax);
     a.blob = field->prepared;
     a.appearance = field->appearance;
-    a.avg = field->average_init_density;
     a.sh_shifted = field->sh_shifted;
-    a.origins = in->origins; a.dirs = in->directions; a.nears = in->nears; a.fars = in->fars;
-    a.cam = in->camera_indices;
-    a.spacing = spacing_ws;
-    a.R = num_rays; a.S = cfg->num_nerf_samples; a.training = cfg->training; a.lin = cfg->initial_sampler == 1;
-    a.rgb = out->rgb; a.acc = out->accumulation; a.depth = out->depth; a.expected = out->expected_depth;
-    a.thermal = out->thermal; a.out_w = out->weights[2]; a.minmax = minmax;
+    a.cam = in->camera_indices; a.training = cfg->training; a.out_w = out->weights[2];
     a.early_eps = cfg->training ? 0.0f : fminf(fmaxf(cfg->early_stop_transmittance, 0.0f), 0.25f);
     a.split = 1; a.seg_len = a.S; a.seg_rec = nullptr; a.seg_cum = nullptr;
     const size_t smem = (size_t)LDS_FLOATS * sizeof(float);
-    const long long cap = 256LL * 2;  // 2 resident blocks per CU (LDS 77 KB each)
     const size_t smem_rays = (size_t)RAYS_LDS_FLOATS * sizeof(float);
-    const long long cap_rays = 256;  // main_mfma_rays_kernel: 1 resident block of 8 waves per CU (LDS 155 KB)
     // 1.5 ms floor of the tile march vs 0.16 ms at 4096 rays
     const bool small_call = tn_render_kernel_form(field, cfg, num_rays, 1) == 2;
     if (!cfg->training && !out->weights[2] && !small_call) {
         // eval: lane = ray (64 consecutive rays per wave), coherent gathers
         const bool dense = a.g.num_dense >= kFieldDense;  // the dense variant reads exactly kFieldDense levels densely
-        if (split > 1 && seg_scratch && a.early_eps == 0.0f) {
-            const long long groups = (num_rays + 63) / 64;
+        const long long groups = (long long)ws.tiles;
+        if (split > 1 && a.early_eps == 0.0f) {
             a.seg_len = (a.S + split - 1) / split;
             a.split = (a.S + a.seg_len - 1) / a.seg_len;  // (no empty segment)
-            a.seg_rec = seg_scratch;
-            a.seg_cum = seg_scratch + (size_t)groups * a.split * SEG_ROWS * 64;
-            if (!(dense ? tn_ensure_dynamic_lds<main_mfma_rays_kernel<true, true>>(smem_rays)
-                        : tn_ensure_dynamic_lds<main_mfma_rays_kernel<false, true>>(smem_rays)))
+            a.seg_rec = ws.at(workspace, ws.scratch);
+            a.seg_cum = ws.at(workspace, ws.seg_cum(a.split));
+            if (!tn_launch_variant_lds<main_mfma_rays_kernel<true, true>, main_mfma_rays_kernel<false, true>>(
+                    dense, tn_grid_blocks(groups * a.split, kRaysWaves, kRaysMaxBlocks), kRaysBlock, smem_rays, stream, a))
                 return TN_ERR_LAUNCH;
-            const long long need = (groups * a.split + kRaysWaves - 1) / kRaysWaves;
-            const unsigned grid = (unsigned)(need < cap_rays ? (need < 1 ? 1 : need) : cap_rays);
-            if (dense)
-                hipLaunchKernelGGL((main_mfma_rays_kernel<true, true>), dim3(grid), dim3(kRaysBlock), smem_rays, stream, a);
-            else
-                hipLaunchKernelGGL((main_mfma_rays_kernel<false, true>), dim3(grid), dim3(kRaysBlock), smem_rays, stream, a);
             hipLaunchKernelGGL(segments_combine_kernel, dim3((unsigned)((num_rays + 255) / 256)), dim3(256), 0, stream, a);
-            if (hipGetLastError() != hipSuccess) return TN_ERR_LAUNCH;
+            TN_LAUNCH_CHECK();
             return TN_OK;
         }
-        a.split = 1;
-        if (!(dense ? tn_ensure_dynamic_lds<main_mfma_rays_kernel<true>>(smem_rays) : tn_ensure_dynamic_lds<main_mfma_rays_kernel<false>>(smem_rays)))
-            return TN_ERR_LAUNCH;
-        const long long groups = (num_rays + 63) / 64;
         // (tail_slots: the test hook of tn_render_config — a grid of fewer blocks, so that a few thousand rays are several rounds)
-        const long long cap_blocks = tail_slots > 0 ? (tail_slots + kRaysWaves - 1) / kRaysWaves : cap_rays;
+        const long long cap_blocks = cfg->tail_slots > 0 ? (cfg->tail_slots + kRaysWaves - 1) / kRaysWaves : kRaysMaxBlocks;
         const long long slots = cap_blocks * kRaysWaves, full = groups / slots * slots, rem = groups - full;
-        if (tail_k > 1 && tail_rec && full > 0 && rem > 0 && a.early_eps == 0.0f) {
+        if (tail_k > 1 && full > 0 && rem > 0 && a.early_eps == 0.0f) {
             // the whole rounds as ever; the last partial round as (tile, segment) records + replay (see field_records_kernel):
             // three launches ordered by the stream alone
-            if (!(dense ? tn_ensure_dynamic_lds<field_records_kernel<true>>(smem_rays) : tn_ensure_dynamic_lds<field_records_kernel<false>>(smem_rays)))
-                return TN_ERR_LAUNCH;
             RecordArgs ra;
             ra.m = a;
             ra.tile0 = full; ra.tiles = rem;
             ra.seg_len = (a.S + tail_k - 1) / tail_k;
             ra.k = (a.S + ra.seg_len - 1) / ra.seg_len;  // (no empty segment)
-            ra.rec = tail_rec;
+            ra.rec = ws.at(workspace, ws.records);
             MfmaArgs whole = a;
             whole.R = full * 64;
-            const long long need_rec = (rem * ra.k + kRaysWaves - 1) / kRaysWaves;
-            const unsigned grid_rec = (unsigned)(need_rec < cap_blocks ? need_rec : cap_blocks);
-            if (dense) {
-                hipLaunchKernelGGL(main_mfma_rays_kernel<true>, dim3((unsigned)cap_blocks), dim3(kRaysBlock), smem_rays, stream, whole);
-                hipLaunchKernelGGL(field_records_kernel<true>, dim3(grid_rec), dim3(kRaysBlock), smem_rays, stream, ra);
-            } else {
-                hipLaunchKernelGGL(main_mfma_rays_kernel<false>, dim3((unsigned)cap_blocks), dim3(kRaysBlock), smem_rays, stream, whole);
-                hipLaunchKernelGGL(field_records_kernel<false>, dim3(grid_rec), dim3(kRaysBlock), smem_rays, stream, ra);
-            }
+            if (!tn_launch_variant_lds<main_mfma_rays_kernel<true>, main_mfma_rays_kernel<false>>(dense, (unsigned)cap_blocks, kRaysBlock,
+                                                                                                   smem_rays, stream, whole) ||
+                !tn_launch_variant_lds<field_records_kernel<true>, field_records_kernel<false>>(
+                    dense, tn_grid_blocks(rem * ra.k, kRaysWaves, cap_blocks), kRaysBlock, smem_rays, stream, ra))
+                return TN_ERR_LAUNCH;
             hipLaunchKernelGGL(field_replay_kernel, dim3((unsigned)((rem + 3) / 4)), dim3(256), 0, stream, ra);
-            if (hipGetLastError() != hipSuccess) return TN_ERR_LAUNCH;
+            TN_LAUNCH_CHECK();
             return TN_OK;
         }
-        const long long need = (groups + kRaysWaves - 1) / kRaysWaves;
-        const unsigned grid = (unsigned)(need < cap_blocks ? (need < 1 ? 1 : need) : cap_blocks);
-        if (dense)
-            hipLaunchKernelGGL(main_mfma_rays_kernel<true>, dim3(grid), dim3(kRaysBlock), smem_rays, stream, a);
-        else
-            hipLaunchKernelGGL(main_mfma_rays_kernel<false>, dim3(grid), dim3(kRaysBlock), smem_rays, stream, a);
-        if (hipGetLastError() != hipSuccess) return TN_ERR_LAUNCH;
+        if (!tn_launch_variant_lds<main_mfma_rays_kernel<true>, main_mfma_rays_kernel<false>>(
+                dense, tn_grid_blocks(groups, kRaysWaves, cap_blocks), kRaysBlock, smem_rays, stream, a))
+            return TN_ERR_LAUNCH;
+        TN_LAUNCH_CHECK();
         return TN_OK;
     }
     if (!tn_ensure_dynamic_lds<main_mfma_kernel>(smem)) return TN_ERR_LAUNCH;
-    const long long need = (num_rays + kWaves - 1) / kWaves;
-    const unsigned grid = (unsigned)(need < cap ? (need < 1 ? 1 : need) : cap);
-    hipLaunchKernelGGL(main_mfma_kernel, dim3(grid), dim3(kBlock), smem, stream, a);
-    if (hipGetLastError() != hipSuccess) return TN_ERR_LAUNCH;
+    hipLaunchKernelGGL(main_mfma_kernel, dim3(tn_grid_blocks(num_rays, kWaves, kMainMfmaMaxBlocks)), dim3(kBlock), smem, stream, a);
+    TN_LAUNCH_CHECK();
     return TN_OK;
 }
 
@@ -1516,11 +1488,9 @@ int tn_field_fwd_taped(const tn_thermal_field *f, const float *positions, const 
     TN_TRY(tn_check_thermal_field(f));
     if (!mfma_supported(f) || !f->prepared) return TN_ERR_UNSUPPORTED;
     TapedArgs a;
-    a.g = tn_make_grid(f->grid);
-    a.space = f->space;
+    fill_field_args(a, f);
     a.blob = f->prepared;
     a.appearance = f->appearance;
-    a.avg = f->average_init_density;
     a.sh_shifted = f->sh_shifted;
     a.positions = positions; a.dirs = directions; a.cam = camera_indices;
     a.N = (long long)num_rays * n; a.n = n;
@@ -1528,11 +1498,9 @@ int tn_field_fwd_taped(const tn_thermal_field *f, const float *positions, const 
     a.t1 = t1; a.t2 = t2; a.thermal = thermal; a.ray_bias = nullptr; a.jac = nullptr;
     const size_t smem = (size_t)LDS_FLOATS * sizeof(float);
     if (!tn_ensure_dynamic_lds<field_fwd_taped_kernel<true>>(smem)) return TN_ERR_LAUNCH;
-    const long long passes = (a.N + 63) / 64;
-    const long long need = (passes + kWaves - 1) / kWaves;
-    const unsigned grid = (unsigned)(need < 512 ? (need < 1 ? 1 : need) : 512);
+    const unsigned grid = tn_grid_blocks((a.N + 63) / 64, kWaves, kTapedMaxBlocks);
     hipLaunchKernelGGL(field_fwd_taped_kernel<true>, dim3(grid), dim3(kBlock), smem, (hipStream_t)stream, a);
-    if (hipGetLastError() != hipSuccess) return TN_ERR_LAUNCH;
+    TN_LAUNCH_CHECK();
     return TN_OK;
 }
 
@@ -1545,11 +1513,9 @@ int tn_field_fwd_train(const tn_thermal_field *f, const float *positions, const 
     TN_TRY(tn_check_thermal_field(f));
     if (!mfma_supported(f) || !f->prepared) return TN_ERR_UNSUPPORTED;
     TapedArgs a;
-    a.g = tn_make_grid(f->grid);
-    a.space = f->space;
+    fill_field_args(a, f);
     a.blob = f->prepared;
     a.appearance = f->appearance;
-    a.avg = f->average_init_density;
     a.sh_shifted = f->sh_shifted;
     a.positions = positions; a.dirs = nullptr; a.cam = nullptr;
     a.N = (long long)num_rays * n; a.n = n;
@@ -1558,12 +1524,10 @@ int tn_field_fwd_train(const tn_thermal_field *f, const float *positions, const 
     const size_t smem = (size_t)LDS_FLOATS * sizeof(float);
     if (!tn_ensure_dynamic_lds<field_fwd_taped_kernel<false>>(smem) || !tn_ensure_dynamic_lds<field_fwd_taped_kernel<false, true>>(smem))
         return TN_ERR_LAUNCH;
-    const long long passes = (a.N + 63) / 64;
-    const long long need = (passes + kWaves - 1) / kWaves;
-    const unsigned grid = (unsigned)(need < 512 ? (need < 1 ? 1 : need) : 512);
+    const unsigned grid = tn_grid_blocks((a.N + 63) / 64, kWaves, kTapedMaxBlocks);
     if (a.jac) hipLaunchKernelGGL((field_fwd_taped_kernel<false, true>), dim3(grid), dim3(kBlock), smem, (hipStream_t)stream, a);
     else hipLaunchKernelGGL(field_fwd_taped_kernel<false>, dim3(grid), dim3(kBlock), smem, (hipStream_t)stream, a);
-    if (hipGetLastError() != hipSuccess) return TN_ERR_LAUNCH;
+    TN_LAUNCH_CHECK();
     return TN_OK;
 }
 
@@ -1577,15 +1541,9 @@ int tn_field_prepare(const tn_thermal_field *f, void *prepared_dev, size_t bytes
     TN_TRY(tn_check_thermal_field(f));
     if (!mfma_supported(f)) return TN_ERR_UNSUPPORTED;
     if (bytes < (size_t)BLOB_FLOATS * sizeof(float)) return TN_ERR_WORKSPACE;
-    RawField w;
-    w.b0w = f->base0.weight; w.b0b = f->base0.bias; w.b1w = f->base1.weight; w.b1b = f->base1.bias;
-    w.h0w = f->head0.weight; w.h0b = f->head0.bias; w.h1w = f->head1.weight; w.h1b = f->head1.bias;
-    w.h2w = f->head2.weight; w.h2b = f->head2.bias; w.t0w = f->th0.weight; w.t0b = f->th0.bias;
-    w.t1w = f->th1.weight; w.t1b = f->th1.bias; w.thw = f->thead.weight; w.thb = f->thead.bias;
-    w.appearance = f->appearance; w.num_images = f->num_images; w.use_avg = f->use_average_appearance;
-    hipLaunchKernelGGL(field_prepare_kernel, dim3((BLOB_FLOATS + 255) / 256), dim3(256), 0, (hipStream_t)stream, w,
-                       reinterpret_cast<float *>(prepared_dev));
-    if (hipGetLastError() != hipSuccess) return TN_ERR_LAUNCH;
+    hipLaunchKernelGGL(field_prepare_kernel, dim3((BLOB_FLOATS + 255) / 256), dim3(256), 0, (hipStream_t)stream,
+                       make_raw_field<RawField>(f), reinterpret_cast<float *>(prepared_dev));
+    TN_LAUNCH_CHECK();
     return TN_OK;
 }
 

@@ -14,7 +14,7 @@ import torch
 from torch import Tensor
 
 from . import _hip
-from .samplers import linspace_bins, pdf_positions
+from .render_call import render_config, render_inputs
 from .nerfacto_config.thermal_nerfacto import KERNEL_FAMILY, tail_balance_value
 from .thermal_nerf.thermal_nerf_model import ThermalNerfModel
 
@@ -42,17 +42,7 @@ class RayRenderEngine:
         self.chunk = int(chunk or model.config.eval_num_rays_per_chunk)
         self.lib = _hip.load()
         cfg = model.config
-        self.P0, self.P1 = cfg.num_proposal_samples_per_ray
-        self.S = cfg.num_nerf_samples_per_ray
-        self.rc = _hip.tn_render_config()
-        self.rc.num_proposal_samples[0], self.rc.num_proposal_samples[1] = self.P0, self.P1
-        self.rc.num_nerf_samples = self.S
-        self.rc.training = 0
-        self.rc.pdf_anneal = float(model.proposal_sampler._anneal)
-        self.rc.early_stop_transmittance = float(cfg.early_termination_eps)
-        self.rc.kernel_family = 0
-        self.rc.initial_sampler = int(model.proposal_sampler.initial_sampler.uniform_spacing)
-        self.rc.tail_balance = tail_balance_value(getattr(cfg, "tail_balance", "auto"))
+        self.rc = render_config(model, False, tail_balance=tail_balance_value(cfg.tail_balance))
         self._budget = int(max_workspace_bytes)
         self.fuse_chunks = bool(fuse_chunks) and self.chunk % 64 == 0
         # launches of 65 536 rays are 1024 waves — one per SIMD, half of what the field kernel needs to hide its gathers —
@@ -106,15 +96,6 @@ class RayRenderEngine:
         for k in OUTPUT_KEYS[1:]:
             out[k] = torch.empty((n, 1), dtype=torch.float32, device=dev)
         return out
-
-    def _inputs(self, dev):
-        ins = _hip.tn_render_inputs()
-        ins.camera_indices = None
-        ins.jitter = None
-        ins.lin_bins0 = linspace_bins(self.P0, dev).data_ptr()
-        ins.u1 = pdf_positions(self.P1 + 1, dev, False).data_ptr()
-        ins.u2 = pdf_positions(self.S + 1, dev, False).data_ptr()
-        return ins
 
     def frame_launch_rays(self, frame_rays: int) -> int:
         """Rays per launch pair of a ``frame_rays``-ray frame: the frame if its workspace fits the budget, else equal runs of whole
@@ -224,7 +205,7 @@ class RayRenderEngine:
                       need=self._workspace_need(fld, pieces, n, sample_split, tail_balance))
         if out is None:
             out = self.allocate_outputs(n, dev)
-        ins = self._inputs(dev)
+        ins = render_inputs(self.rc, dev)
         if (nears is None) != (fars is None):
             raise ValueError("pass both nears and fars, or neither")
         if nears is not None:
@@ -324,7 +305,7 @@ class RayRenderEngine:
         self._buffers(dev, max((j - i for i, j in pieces), default=1), len(pieces),
                       need=self._workspace_need(fld, pieces, frame_rays, sample_split, tail_balance))
         tail_saved, self.rc.tail_balance = self.rc.tail_balance, self._tail_request(tail_balance)
-        ins = self._inputs(dev)
+        ins = render_inputs(self.rc, dev)
         ins.nears, ins.fars = self._nf[0].data_ptr(), self._nf[1].data_ptr()
         outs = _hip.tn_render_outputs()
         wsn = self._ws.shape[1]

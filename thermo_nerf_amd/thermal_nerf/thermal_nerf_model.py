@@ -24,10 +24,10 @@ from .. import _hip
 from ..fields import FieldHeadNames, HashMLPDensityField
 from ..nerfacto_config.thermal_nerfacto import KERNEL_FAMILY, tail_balance_value, ThermalNerfactoModel, ThermalNerfactoModelConfig
 from ..rays import RayBundle
+from ..render_call import render_config, render_inputs
 from ..rendered_image_modalities import RenderedImageModality
 from ..renderers import AccumulationRenderer, DepthRenderer, RGBRenderer
-from ..samplers import (ProposalNetworkSampler, UniformSampler, draw_jitter, jitter_levels, linspace_bins, pdf_positions,
-                        _samples_from_bins)
+from ..samplers import ProposalNetworkSampler, UniformSampler, draw_jitter, jitter_levels, _samples_from_bins
 from ..scene import NearFarCollider, SceneBox, SceneContraction
 from .thermal_field import ThermalNerfactoTField
 from .thermal_field_head import FieldHeadNamesT
@@ -412,20 +412,8 @@ class ThermalNerfModel(ThermalNerfactoModel):
         S = cfg.num_nerf_samples_per_ray
         prop0, prop1, fld = self._c_structs()
 
-        rc = _hip.tn_render_config()
-        rc.num_proposal_samples[0], rc.num_proposal_samples[1] = P0, P1
-        rc.num_nerf_samples = S
-        rc.training = 1 if training else 0
-        rc.pdf_anneal = float(self.proposal_sampler._anneal)
-        rc.early_stop_transmittance = 0.0 if training else float(cfg.early_termination_eps)
-        rc.kernel_family = KERNEL_FAMILY[cfg.kernel_family]
-        rc.initial_sampler = int(self.proposal_sampler.initial_sampler.uniform_spacing)
-        rc.sample_split = int(getattr(cfg, "sample_split", 0))
-        rc.per_sample_jitter = 0 if cfg.use_single_jitter else 1
-        rc.tail_balance = tail_balance_value(getattr(cfg, "tail_balance", "auto"))
-
-        ins = _hip.tn_render_inputs()
-        ins.origins, ins.directions, ins.nears, ins.fars = o.data_ptr(), d.data_ptr(), nears.data_ptr(), fars.data_ptr()
+        rc = render_config(self, training, kernel_family=KERNEL_FAMILY[cfg.kernel_family], sample_split=int(cfg.sample_split),
+                           per_sample_jitter=0 if cfg.use_single_jitter else 1, tail_balance=tail_balance_value(cfg.tail_balance))
         cam = None
         if training:
             if ray_bundle.camera_indices is None:
@@ -435,11 +423,7 @@ class ThermalNerfModel(ThermalNerfactoModel):
             if jitter is None:
                 jitter = draw_jitter(R, (P0, P1, S), bool(cfg.use_single_jitter), dev)
             jitter = jitter_levels(jitter, R, (P0, P1, S), bool(cfg.use_single_jitter))[0]
-        ins.camera_indices = _hip.ptr(cam)
-        ins.jitter = _hip.ptr(jitter) if training else None
-        ins.lin_bins0 = linspace_bins(P0, dev).data_ptr()
-        ins.u1 = pdf_positions(P1 + 1, dev, training).data_ptr()
-        ins.u2 = pdf_positions(S + 1, dev, training).data_ptr()
+        ins = render_inputs(rc, dev, (o, d, nears, fars), cam, jitter if training else None)
 
         buf = torch.empty((9, R), dtype=torch.float32, device=dev)  # 36 B/ray of outputs, one allocation
         rgb = torch.empty((R, 3), dtype=torch.float32, device=dev)

@@ -24,6 +24,7 @@ from torch import Tensor
 
 from . import _hip
 from .rays import RayBundle
+from .render_call import render_config, render_inputs
 from .samplers import LazyRaySamples, draw_jitter, jitter_levels, linspace_bins, pdf_positions
 
 ACT_NONE, ACT_RELU, ACT_SIGMOID = 0, 1, 2
@@ -476,18 +477,9 @@ class RenderTrain(torch.autograd.Function):
             # needed, so both levels run as ONE fused kernel (tn_proposal_sample_fwd, train-mode semantics)
             if _step_call_applies(model, cfg):
                 # ... and the whole forward chain of such a step as ONE C-ABI call (tn_train_step_fwd, round 6)
-                return _StepCall.forward(ctx, model, o, d, nears, fars, cam, jitter, params, prop_structs, anneal, uniform, single)
-            rc = _hip.tn_render_config()
-            rc.num_proposal_samples[0], rc.num_proposal_samples[1], rc.num_nerf_samples = P[0], P[1], S
-            rc.training, rc.pdf_anneal, rc.early_stop_transmittance, rc.kernel_family = 1, anneal, 0.0, 0
-            rc.initial_sampler = uniform
-            rc.per_sample_jitter = 0 if single else 1
-            ins = _hip.tn_render_inputs()
-            ins.origins, ins.directions, ins.nears, ins.fars = o.data_ptr(), d.data_ptr(), nears.data_ptr(), fars.data_ptr()
-            ins.camera_indices, ins.jitter = cam.data_ptr(), jitter.data_ptr()
-            ins.lin_bins0 = linspace_bins(P[0], dev).data_ptr()
-            ins.u1 = pdf_positions(P[1] + 1, dev, True).data_ptr()
-            ins.u2 = pdf_positions(S + 1, dev, True).data_ptr()
+                return _StepCall.forward(ctx, model, o, d, nears, fars, cam, jitter, params, prop_structs, single)
+            rc = render_config(model, True, per_sample_jitter=0 if single else 1)
+            ins = render_inputs(rc, dev, (o, d, nears, fars), cam, jitter)
             outs = _hip.tn_render_outputs()
             ns = (P[0], P[1], S)
             sp = [_f32((R, k + 1), dev) for k in ns]
@@ -842,13 +834,22 @@ def _al(n: int) -> int:
     return (n + 63) // 64 * 64  # 256-byte aligned carve-outs
 
 
+def _slab_layout(sizes):
+    """(name, floats) in slab order -> ({name: offset in floats}, floats of the slab)"""
+    off, total = {}, 0
+    for name, n in sizes:
+        off[name] = total
+        total += _al(n)
+    return off, total
+
+
 class _StepCall:
     """RenderTrain's forward / backward on a step whose proposal networks take no gradient, each as ONE library call.  The
     per-sample tensors of the step live in one slab (they are only ever passed on as addresses), the per-ray outputs in another
     (the tensors autograd hands back to the caller must not keep ~150 B per sample alive)."""
 
     @staticmethod
-    def forward(ctx, model, o, d, nears, fars, cam, jitter, params, prop_structs, anneal, uniform, single):
+    def forward(ctx, model, o, d, nears, fars, cam, jitter, params, prop_structs, single):
         lib = _hip.load()
         cfg = model.config
         dev = o.device
@@ -876,27 +877,16 @@ class _StepCall:
         mult_d, mult_i = float(cfg.distortion_loss_mult), float(cfg.interlevel_loss_mult)
         if want:
             shapes += [("g_dist", (R, S)), ("g_i0", (R, P0)), ("g_i1", (R, P1))]
-        off, total = {}, 0
-        for name, shp in shapes:
-            off[name] = total
-            total += _al(shp[0] * shp[1])
+        off, total = _slab_layout((name, shp[0] * shp[1]) for name, shp in shapes)
         ray_slab = torch.empty((total,), dtype=torch.float32, device=dev)
         t = {name: ray_slab[off[name]:off[name] + shp[0] * shp[1]].view(shp) for name, shp in shapes}
         # ---- per-sample slab: addresses only -------------------------------------------------------------------------------------
-        need_ws = 0
-        rc = _hip.tn_render_config()
-        rc.num_proposal_samples[0], rc.num_proposal_samples[1], rc.num_nerf_samples = P0, P1, S
-        rc.training, rc.pdf_anneal, rc.early_stop_transmittance, rc.kernel_family = 1, anneal, 0.0, 0
-        rc.initial_sampler = uniform
-        rc.per_sample_jitter = 0 if single else 1
+        rc = render_config(model, True, per_sample_jitter=0 if single else 1)
         need_ws = lib.tn_render_workspace_bytes(rc, R)
         sizes = [("pos", N * 3), ("starts", N), ("ends", N), ("deltas", N), ("ray_bias", R * 64), ("enc", NP * 32), ("sel", N),
                  ("density", N), ("rgb_s", N * 3), ("th_s", N), ("base_out", N * 16 if keep_base else 0),
                  ("jac", NP * 96 if keep_jac else 0), ("scratch", 2 * ((R + 3) // 4)), ("ws", (need_ws + 3) // 4)]
-        so, stotal = {}, 0
-        for name, n in sizes:
-            so[name] = stotal
-            stotal += _al(n)
+        so, stotal = _slab_layout(sizes)
         slab = torch.empty((stotal,), dtype=torch.float32, device=dev)
         base = slab.data_ptr()
 
@@ -906,12 +896,7 @@ class _StepCall:
         st = _hip.tn_train_step()
         st.prop0, st.prop1 = C.pointer(prop_structs[0]), C.pointer(prop_structs[1])
         st.field_raw, st.field, st.prepared_bytes = C.pointer(raw), C.pointer(prepared), prepared_bytes
-        ins = _hip.tn_render_inputs()
-        ins.origins, ins.directions, ins.nears, ins.fars = o.data_ptr(), d.data_ptr(), nears.data_ptr(), fars.data_ptr()
-        ins.camera_indices, ins.jitter = cam.data_ptr(), jitter.data_ptr()
-        ins.lin_bins0 = linspace_bins(P0, dev).data_ptr()
-        ins.u1 = pdf_positions(P1 + 1, dev, True).data_ptr()
-        ins.u2 = pdf_positions(S + 1, dev, True).data_ptr()
+        ins = render_inputs(rc, dev, (o, d, nears, fars), cam, jitter)
         st.cfg, st.inputs, st.num_rays = C.pointer(rc), C.pointer(ins), R
         for i in range(3):
             st.spacing[i], st.eucl[i], st.weights[i] = t["sp%d" % i].data_ptr(), t["eu%d" % i].data_ptr(), t["w%d" % i].data_ptr()
@@ -1029,10 +1014,7 @@ class _StepCall:
         sizes = [("g_rgb_s", N * 3 if g_rgb is not None else 0), ("g_th_s", N if g_th is not None else 0), ("g_density", N), ("g_enc", N * 32),
                  ("g_pos", N * 3 if ray_grads else 0), ("g_cin", R * 64 if (sh_grads and g_rgb is not None) else 0),
                  ("sorted", (need_sorted + 3) // 4)]
-        bo, btotal = {}, 0
-        for name, n in sizes:
-            bo[name] = btotal
-            btotal += _al(n)
+        bo, btotal = _slab_layout(sizes)
         try:
             bslab = torch.empty((btotal,), dtype=torch.float32, device=dev)
         except torch.cuda.OutOfMemoryError:  # no room for the records: the same sums through the global atomics

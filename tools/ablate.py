@@ -46,7 +46,9 @@ def variant(name: str, src: str) -> str:
         v = v.replace("lds[OFF_W_APP + k * 64 + lane]", "lds[128 + lane]")
         v = v.replace("float *scratch = lds + OFF_SCRATCH + wave * 64;", "float *scratch = lds + 1024 + wave * 64;")
         v = v.replace("const size_t smem = (size_t)LDS_FLOATS * sizeof(float);", "const size_t smem = 8192;")
-        v = v.replace("const long long cap = 256LL * 2;", "const long long cap = 256LL * 8;")
+        old = "constexpr long long kMainMfmaMaxBlocks = kCUs * 2;"
+        assert v.count(old) == 1
+        v = v.replace(old, "constexpr long long kMainMfmaMaxBlocks = kCUs * 8;")
         v = v.replace("__launch_bounds__(kBlock, 2)", "__launch_bounds__(kBlock, 8)")
         return v
     if name == "nomlp_8lv":  # no MLP, only the 8 finest levels hashed
