@@ -16,8 +16,11 @@ SH basis when a camera optimizer makes them depend on ``pose_adjustment``.  Not 
 from __future__ import annotations
 
 import ctypes as C
+import math
 import threading
-from typing import Dict, List, Optional, Sequence, Tuple
+from collections import namedtuple
+from dataclasses import dataclass, replace
+from typing import Dict, List, Optional, Sequence, Tuple, Union
 
 import torch
 from torch import Tensor
@@ -35,26 +38,63 @@ def _f32(shape, dev) -> Tensor:
 
 
 class _StreamOverride(threading.local):
-    """per thread (autograd runs a device's backward on its own thread): [raw stream handle or None]"""
+    """per thread (autograd runs a device's backward on its own thread): the raw stream handle launches are forced to, or None"""
 
-    def __init__(self) -> None:
-        self.slot: List[Optional[int]] = [None]
-
-    def __getitem__(self, k: int) -> Optional[int]:
-        return self.slot[k]
-
-    def __setitem__(self, k: int, v: Optional[int]) -> None:
-        self.slot[k] = v
+    handle: Optional[int] = None
 
 
 _STREAM_OVERRIDE = _StreamOverride()
+
+
+@dataclass(frozen=True)
+class _StepOptions:
+    """The config switches of the training step, read ONCE per forward and once per backward (never cached on the model: the
+    switches may change between steps), with every condition that combines them resolved here."""
+
+    fused_proposal: bool  # proposal levels of an update step: encode + MLP + trunc_exp in one launch each way
+    tape_free: bool  # final level without an activation tape (needs the MFMA chain's geometry: the forward decides)
+    fused_forward: bool  # taped final level: the forward as one launch
+    chained: bool  # taped backward: each MLP's layers in ONE launch (tn_linear_chain_bwd; it tiles 64-wide layers) vs one per layer
+    split_form: int  # tn_field_bwd_fused: 0 one launch; 1 colour head | thermal head | mlp_base; 2 the same with bf16 pieces
+    keep_base: bool  # the forward stores mlp_base's output rows for the split backward
+    keep_jac: bool  # ... and d hash features / d position, when the rays carry gradient
+    bucketed: Union[bool, int]  # table scatter: False atomics | True from the level the library advises | int from that level
+    spread: bool  # coarsest atomic levels through private dense copies
+    overlap: bool  # the scatter's bucketed part (and an update step's proposal backward) on the step's side streams
+    defer: bool  # ... and not joined by the backward (only with overlap; the scatter adds: and only with a bucketed part)
+    exp_min: float  # trunc_exp backward clamp
+    regularisers: bool  # the two regularisers launched by the forward on the side streams ("auto" resolved)
+    step_call: bool  # a step without proposal gradients as ONE library call each way (tn_train_step_fwd / _bwd)
+
+
+def _step_options(model, cfg, R: int, S: int, rays_need_grad: bool) -> _StepOptions:
+    split = bool(cfg.fused_backward_split)
+    tape_free = bool(cfg.tape_free_training)
+    overlap = bool(cfg.overlap_table_scatter)
+    regularisers = cfg.overlap_regularisers
+    if regularisers == "auto":
+        # the side launches cost the host four stream joins (~40 us): they pay once the step's device time is well above its
+        # host time — S=192: 2.64 against 2.68 ms per step; S=48 (device 1.34 ms, host ~1 ms): 1.34-1.46 against 1.34-1.35
+        regularisers = R * S >= 4096 * 96
+    return _StepOptions(
+        fused_proposal=bool(cfg.fused_proposal_training), tape_free=tape_free, fused_forward=bool(cfg.fused_train_forward),
+        chained=bool(cfg.fused_train_backward) and not model.field.staged,
+        split_form=0 if not split else (2 if cfg.backward_bf16_pieces else 1),
+        # (the one-launch backward needs the hidden layer anyway and reads the table for the position gradient)
+        keep_base=split and bool(cfg.store_base_output),
+        keep_jac=split and bool(rays_need_grad) and bool(cfg.store_position_jacobian),
+        bucketed=cfg.bucketed_table_scatter, spread=bool(cfg.spread_coarse_scatter), overlap=overlap,
+        defer=bool(cfg.deferred_table_update) and overlap, exp_min=float(cfg.trunc_exp_clamp_min), regularisers=bool(regularisers),
+        # the default training configuration: tape-free final level, split backward; any other setting keeps the per-call path
+        # (which is also the cross-check: same launches, same streams, same bits)
+        step_call=bool(cfg.fused_step_calls) and tape_free and split and cfg.num_proposal_iterations == 2 and not model.field.staged)
 
 
 def _stream():
     """the HIP stream the next launch goes to: torch's current stream, or the second stream of the step while its section of
     the backward is being queued (set explicitly: `with torch.cuda.stream(...)` costs ~0.1 ms of host time per use — its
     enter / exit look the current device up through torch.cuda.is_available() and os.environ)"""
-    forced = _STREAM_OVERRIDE[0]
+    forced = _STREAM_OVERRIDE.handle
     return _hip.current_stream() if forced is None else forced
 
 
@@ -70,19 +110,31 @@ def hash_encode_fwd(grid, space, pos: Tensor) -> Tuple[Tensor, Tensor]:
     return enc, sel
 
 
-_SPREAD_WS: Dict = {}
+_WORKSPACES: Dict = {}
+
+
+def _workspace(kind, dev, stream: int, need, grow: bool = False) -> Tensor:
+    """the scratch buffer of one kind of launch per (device, stream): calls on one stream are ordered, so they share one buffer; two
+    streams must not.  ``need``: bytes, or a callable that says (asked on a miss only); ``grow``: reallocated when a call needs more."""
+    key = (kind, dev, stream)
+    ws = _WORKSPACES.get(key)
+    if ws is None or (grow and ws.numel() < need):
+        ws = _WORKSPACES[key] = torch.empty(need() if callable(need) else need, dtype=torch.uint8, device=dev)
+    return ws
+
+
+def _spread_workspace(lib, grid, dev, stream: int) -> Tuple[Optional[Tensor], int]:
+    """the private dense copies of tn_hash_encode_bwd_spread on ``stream`` (one buffer per size: the grids differ), or (None, 0)"""
+    need = lib.tn_hash_encode_bwd_spread_workspace_bytes(grid)
+    return (_workspace(("spread", need), dev, stream, need), need) if need else (None, 0)
 
 
 def _atomic_levels(lib, grid, space, pos: Tensor, d_enc: Tensor, d_table: Tensor, lo: int, hi: int, spread: bool) -> None:
     """levels [lo, hi) with global atomics; ``spread``: the coarsest levels through private dense copies (tn_hash_encode_bwd_spread)"""
     n = pos.shape[0]
     args = (grid, space, pos.data_ptr(), d_enc.data_ptr(), n, d_table.data_ptr(), lo, hi)
-    need = lib.tn_hash_encode_bwd_spread_workspace_bytes(grid) if spread and lo == 0 else 0
+    ws, need = _spread_workspace(lib, grid, pos.device, _stream()) if spread and lo == 0 else (None, 0)
     if need:
-        key = (pos.device, _stream(), need)
-        ws = _SPREAD_WS.get(key)
-        if ws is None:
-            ws = _SPREAD_WS[key] = torch.empty(need, dtype=torch.uint8, device=pos.device)
         _hip.check(lib.tn_hash_encode_bwd_spread(*args, ws.data_ptr(), need, _stream()), "tn_hash_encode_bwd_spread")
     else:
         _hip.check(lib.tn_hash_encode_bwd_levels(*args, _stream()), "tn_hash_encode_bwd_levels")
@@ -104,6 +156,17 @@ def _step_streams(dev) -> Tuple["torch.cuda.Stream", "torch.cuda.Stream", "torch
     return trio
 
 
+def _sorted_plan(lib, grid, n: int, bucketed) -> Tuple[int, int]:
+    """(first bucketed level or -1, bytes of the record workspace) for ``bucketed`` = False | True (the level the library advises) |
+    an int (tests, tools/train_bench.py --first-sorted-level: bucketed from that level on)"""
+    first = -1
+    if bucketed is True:
+        first = lib.tn_hash_encode_bwd_sorted_first_level(grid, n)
+    elif bucketed is not False and bucketed is not None:
+        first = int(bucketed)
+    return first, (lib.tn_hash_encode_bwd_sorted_workspace_bytes(grid, n, first) if first >= 0 else 0)
+
+
 def hash_encode_bwd(grid, space, pos: Tensor, d_enc: Tensor, d_table: Tensor, bucketed=False, spread: bool = True,
                     overlap: bool = False, side_work=None, keep: Optional[list] = None, defer: bool = False) -> bool:
     """d_table += adjoint of the hash encoding.  ``bucketed=False``: the global-atomic scatter (tn_hash_encode_bwd).
@@ -123,69 +186,60 @@ def hash_encode_bwd(grid, space, pos: Tensor, d_enc: Tensor, d_table: Tensor, bu
     to the second, the atomic one to the third — and the calling stream does not wait for them: it runs ``side_work`` and returns
     True; the join is the caller's business (_hip.defer / _hip.join_pending hold the temporaries until then).  Returns False when
     the scatter was joined as usual."""
-    if side_work is not None and not overlap:
-        hash_encode_bwd(grid, space, pos, d_enc, d_table, bucketed, spread, keep=keep)
-        side_work()
-        return False
     lib = _hip.load()
-    n = pos.shape[0]
-    first = -1
-    if bucketed is True:
-        first = lib.tn_hash_encode_bwd_sorted_first_level(grid, n)
-    elif bucketed is not False and bucketed is not None:
-        first = int(bucketed)
-    need = lib.tn_hash_encode_bwd_sorted_workspace_bytes(grid, n, first) if first >= 0 else 0
-    if not need:
-        _atomic_levels(lib, grid, space, pos, d_enc, d_table, 0, grid.num_levels, spread)
-        if side_work is not None:
-            side_work()
-        return False
-    try:
-        ws = torch.empty(need, dtype=torch.uint8, device=pos.device)  # 25 B per (sample, level, corner pair): 0.14-0.6 GB, from torch's caching allocator
-        if keep is not None:
-            keep.append(ws)
-    except torch.cuda.OutOfMemoryError:  # no room for the records: the same sums through the global atomics
-        _atomic_levels(lib, grid, space, pos, d_enc, d_table, 0, first, spread)
-        _hip.check(lib.tn_hash_encode_bwd_levels(grid, space, pos.data_ptr(), d_enc.data_ptr(), n, d_table.data_ptr(), first,
-                                                 grid.num_levels, _stream()), "tn_hash_encode_bwd_levels")
-        if side_work is not None:
-            side_work()
-        return False
-    if overlap and first > 0 and defer:
-        main, side, third = _step_streams(pos.device)
-        side.wait_stream(main)  # d_enc, positions and the cleared d_table are the main stream's work so far
-        third.wait_stream(main)
-        _hip.check(lib.tn_hash_encode_bwd_sorted(grid, space, pos.data_ptr(), d_enc.data_ptr(), n, d_table.data_ptr(), first,
-                                                 ws.data_ptr(), need, side.cuda_stream), "tn_hash_encode_bwd_sorted")
-        saved = _STREAM_OVERRIDE[0]
-        _STREAM_OVERRIDE[0] = third.cuda_stream  # (the spread copies' workspace is keyed by the stream: the third's own)
+    n, L = pos.shape[0], grid.num_levels
+    # ---- plan: levels [0, split) through the atomics, [split, L) as records — or through the atomics too, without room for them
+    first, need = _sorted_plan(lib, grid, n, bucketed)
+    ws = None
+    if need:
         try:
-            _atomic_levels(lib, grid, space, pos, d_enc, d_table, 0, first, spread)
+            ws = torch.empty(need, dtype=torch.uint8, device=pos.device)  # 25 B per (sample, level, corner pair): 0.14-0.6 GB, from torch's caching allocator
+            if keep is not None:
+                keep.append(ws)
+        except torch.cuda.OutOfMemoryError:  # no room for the records: the same sums through the global atomics
+            pass
+    split = first if need else L
+    # ---- schedule: (stream of the bucketed part, stream of the atomic part, how the call ends); None = the calling stream / as it is
+    bucketed_on = atomic_on = end = None
+    if ws is not None and overlap and first > 0:
+        main, second, third = _step_streams(pos.device)
+        bucketed_on, atomic_on, end = second, (third if defer else None), ("defer" if defer else "join")
+        second.wait_stream(main)  # d_enc, positions and the cleared d_table are the main stream's work so far
+        if atomic_on is not None:
+            atomic_on.wait_stream(main)
+    args = (grid, space, pos.data_ptr(), d_enc.data_ptr(), n, d_table.data_ptr())
+
+    def bucketed_part() -> None:
+        if ws is not None:
+            _hip.check(lib.tn_hash_encode_bwd_sorted(*args, first, ws.data_ptr(), need, _stream() if bucketed_on is None else bucketed_on.cuda_stream),
+                       "tn_hash_encode_bwd_sorted")
+        elif split < L:
+            _hip.check(lib.tn_hash_encode_bwd_levels(*args, split, L, _stream()), "tn_hash_encode_bwd_levels")
+
+    def atomic_part() -> None:
+        if split == 0:
+            return
+        saved = _STREAM_OVERRIDE.handle
+        if atomic_on is not None:
+            _STREAM_OVERRIDE.handle = atomic_on.cuda_stream  # (the spread copies' workspace is keyed by the stream: the third's own)
+        try:
+            _atomic_levels(lib, grid, space, pos, d_enc, d_table, 0, split, spread)
         finally:
-            _STREAM_OVERRIDE[0] = saved
-        if side_work is not None:
-            side_work()  # on the calling stream, beside both parts
+            _STREAM_OVERRIDE.handle = saved
+
+    # beside each other, the bucketed part goes first (it is the longer of the two: timeline in DESIGN 5.6); on one stream it is last
+    for part in ((bucketed_part, atomic_part) if end else (atomic_part, bucketed_part)):
+        part()
+    if side_work is not None:
+        side_work()  # on the calling stream: behind the atomic part when that is there too, beside both parts when neither is
+    if end == "defer":
         # (NOT d_table itself: autograd's AccumulateGrad takes a returned gradient over without a copy only while nobody else
         # holds that tensor object — a second reference makes it CLONE the table gradient on the calling stream, i.e. before the
         # side streams have written it.  The caller keeps the storage alive through another view: the arena's flat buffer.)
-        _hip.defer(pos.device, [side, third], [ws, pos, d_enc])
+        _hip.defer(pos.device, [second, third], [ws, pos, d_enc])
         return True
-    if overlap and first > 0:
-        main, side, _ = _step_streams(pos.device)
-        side.wait_stream(main)  # d_enc, positions and the cleared d_table are the main stream's work so far
-        _hip.check(lib.tn_hash_encode_bwd_sorted(grid, space, pos.data_ptr(), d_enc.data_ptr(), n, d_table.data_ptr(), first,
-                                                 ws.data_ptr(), need, side.cuda_stream), "tn_hash_encode_bwd_sorted")
-        _atomic_levels(lib, grid, space, pos, d_enc, d_table, 0, first, spread)
-        if side_work is not None:
-            side_work()  # behind the atomic part: the bucketed part is the longer of the two (timeline in DESIGN 5.6)
-        main.wait_stream(side)  # also what keeps `ws`, d_enc and pos (main-stream allocations) from being reused too early
-        return False
-    if first > 0:
-        _atomic_levels(lib, grid, space, pos, d_enc, d_table, 0, first, spread)
-    _hip.check(lib.tn_hash_encode_bwd_sorted(grid, space, pos.data_ptr(), d_enc.data_ptr(), n, d_table.data_ptr(), first, ws.data_ptr(),
-                                             need, _stream()), "tn_hash_encode_bwd_sorted")
-    if side_work is not None:
-        side_work()
+    if end == "join":
+        main.wait_stream(second)  # also what keeps `ws`, d_enc and pos (main-stream allocations) from being reused too early
     return False
 
 
@@ -196,64 +250,38 @@ def linear_fwd(x: Tensor, x_off: int, ldx: int, lin, act: int, n: int) -> Tensor
     return y
 
 
-_LIN_WS: Dict = {}
-
-
-def _linear_workspace(dev) -> Tensor:
-    """per-device scratch for tn_linear_bwd's partial weight gradients (calls on one stream are ordered, so one buffer)"""
-    key = (dev, _stream())
-    ws = _LIN_WS.get(key)
-    if ws is None:
-        ws = torch.empty(_hip.load().tn_linear_bwd_workspace_bytes(), dtype=torch.uint8, device=dev)
-        _LIN_WS[key] = ws
-    return ws
-
-
 def linear_bwd(x: Tensor, x_off: int, ldx: int, y: Optional[Tensor], dy: Tensor, ldy: int, lin, act: int, n: int,
                dx: Optional[Tensor], dx_off: int, lddx: int, accumulate: bool, d_w: Optional[Tensor],
                d_b: Optional[Tensor]) -> None:
-    ws = _linear_workspace(dy.device)
-    _hip.check(_hip.load().tn_linear_bwd(
+    lib = _hip.load()
+    ws = _workspace("linear", dy.device, _stream(), lib.tn_linear_bwd_workspace_bytes)  # partial weight gradients
+    _hip.check(lib.tn_linear_bwd(
         x.data_ptr() + 4 * x_off, ldx, None if y is None else y.data_ptr(), dy.data_ptr(), ldy, lin, act, n,
         None if dx is None else dx.data_ptr() + 4 * dx_off, lddx, 1 if accumulate else 0,
         None if d_w is None else d_w.data_ptr(), None if d_b is None else d_b.data_ptr(), ws.data_ptr(), ws.numel(),
         _stream()), "tn_linear_bwd")
 
 
-_CHAIN_WS: Dict = {}
-_FUSED_WS: Dict = {}
-_ZEROS: Dict = {}
-
-
 def _fused_bwd_workspace(dev, R: int, S: int) -> Tensor:
     """per-device workspace of tn_field_bwd_fused (a slab of parameter gradients per persistent block and launch + the heads'
     adjoints of mlp_base's outputs), grown to the largest batch seen"""
-    need = _hip.load().tn_field_bwd_fused_workspace_bytes(R, S)
-    key = (dev, _stream())
-    ws = _FUSED_WS.get(key)
-    if ws is None or ws.numel() < need:
-        ws = _FUSED_WS[key] = torch.empty(need, dtype=torch.uint8, device=dev)
-    return ws
-
-
-def _zeros_like_cached(dev, n: int) -> Tensor:
-    """a read-only run of n zero floats on ``dev`` (the geo rows of the ray-level mlp_head input)"""
-    z = _ZEROS.get(dev)
-    if z is None or z.numel() < n:
-        z = _ZEROS[dev] = torch.zeros((max(n, 1 << 16),), dtype=torch.float32, device=dev)
-    return z
+    return _workspace("fused", dev, _stream(), _hip.load().tn_field_bwd_fused_workspace_bytes(R, S), grow=True)
 
 
 def linear_chain_bwd(layers, y_top: Optional[Tensor], act_top: int, dy: Tensor, lddy: int, n: int, dx: Optional[Tensor],
-                     dx_off: int, lddx: int, accumulate: bool) -> None:
+                     dx_off: int, lddx: int, accumulate: bool, chained: bool = True) -> None:
     """Backward of consecutive Linear(+activation) layers in one launch.  ``layers``: top (nearest the loss) first, each
-    (tn_linear, x tensor, x column offset, ldx, activation that produced x, d_weight, d_bias)."""
+    (tn_linear, x tensor, x column offset, ldx, activation that produced x, d_weight, d_bias).  ``chained=False``: the same
+    layers as one tn_linear_bwd each (any layer width; the chained launch tiles 64-wide layers)."""
+    if not chained:
+        for k, (lin, x, x_off, ldx, act_x, d_w, d_b) in enumerate(layers):
+            if k == len(layers) - 1:
+                return linear_bwd(x, x_off, ldx, y_top, dy, lddy, lin, act_top, n, dx, dx_off, lddx, accumulate, d_w, d_b)
+            g_x = _f32((n, ldx), dy.device)
+            linear_bwd(x, x_off, ldx, y_top, dy, lddy, lin, act_top, n, g_x, 0, ldx, False, d_w, d_b)
+            y_top, act_top, dy, lddy = x, act_x, g_x, ldx
     lib = _hip.load()
-    dev = dy.device
-    key = (dev, _stream())  # calls on one stream are ordered; two streams must not share the partial-sum slabs
-    ws = _CHAIN_WS.get(key)
-    if ws is None:
-        ws = _CHAIN_WS[key] = torch.empty(lib.tn_linear_chain_bwd_workspace_bytes(), dtype=torch.uint8, device=dev)
+    ws = _workspace("chain", dy.device, _stream(), lib.tn_linear_chain_bwd_workspace_bytes)  # the partial-sum slabs
     arr = (_hip.tn_chain_layer * len(layers))()
     for k, (lin, x, x_off, ldx, act_x, d_w, d_b) in enumerate(layers):
         arr[k].lin = lin
@@ -301,7 +329,7 @@ class _GradArena:
     parameter was ~50 fill launches per step).  A fresh arena per backward: the views become the parameters' .grad and must
     not alias the next step's."""
 
-    def __init__(self, like: Dict[str, Tensor], dev, extra: int = 0, zero: bool = True) -> None:
+    def __init__(self, like: Dict[str, Tensor], dev, R: int, S: int, zero: bool = True) -> None:
         """``zero=False``: the flat buffer is allocated but not cleared — tn_train_step_fwd clears it on the step's second stream
         beside the forward (the 75 MB fill leaves the calling stream's critical path)"""
         self.like, self.dev = like, dev
@@ -310,14 +338,14 @@ class _GradArena:
         for name, p in like.items():
             self.offsets[name] = total
             total += (p.numel() + 63) // 64 * 64  # 256-byte aligned views
-        self._extra = total  # `extra` more zero floats for the step's other zero-initialised buffers (ray gradients, per-ray sums)
+        # a tail of more zero floats for the step's other zero-initialised buffers: ray gradients (two pairs on an update step), the
+        # per-ray sums of mlp_head.0's input
+        self._extra, extra = total, R * (64 + 2 * 64 + S) + 1024
         self.flat = (torch.zeros if zero else torch.empty)((total + extra,), dtype=torch.float32, device=dev)
 
     def zeros(self, shape) -> Tensor:
         """a zero tensor carved from the arena's tail (falls back to a fresh allocation when the tail is used up)"""
-        n = 1
-        for k in shape:
-            n *= k
+        n = math.prod(shape)
         n_al = (n + 63) // 64 * 64
         if self._extra + n_al > self.flat.numel():
             return torch.zeros(shape, dtype=torch.float32, device=self.dev)
@@ -385,9 +413,8 @@ def _ray_grads_from_enc(grid, space, t: _LevelTape, g_enc: Tensor, g_o: Tensor, 
                                             g_d.data_ptr(), _stream()), "tn_frustum_positions_bwd")
 
 
-def _proposal_level_bwd(net_struct, t: _LevelTape, g_w: Tensor, grads: Dict[str, Tensor], prefix: str, like: Dict,
-                        ray_grads: Optional[Tuple[Tensor, Tensor]] = None, chained: bool = True, bucketed: bool = False,
-                        exp_min: float = -15.0, spread: bool = True, keep: Optional[list] = None) -> None:
+def _proposal_level_bwd(net_struct, t: _LevelTape, g_w: Tensor, grads: Dict[str, Tensor], prefix: str, like: "_GradArena",
+                        opts: _StepOptions, ray_grads: Optional[Tuple[Tensor, Tensor]] = None, keep: Optional[list] = None) -> None:
     """``keep``: a list the temporaries are appended to — the caller queues this level on another stream than the allocator's
     and holds them until that stream has been joined (the tape-free / fused form only: no torch op in between)."""
     lib = _hip.load()
@@ -397,8 +424,7 @@ def _proposal_level_bwd(net_struct, t: _LevelTape, g_w: Tensor, grads: Dict[str,
              f"{prefix}.mlp_base.mlp.layers.0.bias", f"{prefix}.mlp_base.mlp.layers.1.weight",
              f"{prefix}.mlp_base.mlp.layers.1.bias"]
     for k in names:
-        if k not in grads:
-            grads[k] = like.get(k)  # `like` is the step's _GradArena: zero-filled views
+        grads.setdefault(k, like.get(k))  # `like` is the step's _GradArena: zero-filled views
     E = t.enc.shape[1]
     g_enc = _f32((n, E), g_w.device)
     if keep is not None:
@@ -406,24 +432,173 @@ def _proposal_level_bwd(net_struct, t: _LevelTape, g_w: Tensor, grads: Dict[str,
     if t.hid is None:
         # the fused forward's counterpart: trunc_exp backward + both Linear layers' adjoints in one launch, hidden layer recomputed
         _hip.check(lib.tn_density_bwd_train(net_struct, t.enc.data_ptr(), t.raw.data_ptr(), t.sel.data_ptr(), g_density.data_ptr(), n,
-                                            exp_min, g_enc.data_ptr(), grads[names[1]].data_ptr(), grads[names[2]].data_ptr(),
+                                            opts.exp_min, g_enc.data_ptr(), grads[names[1]].data_ptr(), grads[names[2]].data_ptr(),
                                             grads[names[3]].data_ptr(), grads[names[4]].data_ptr(), _stream()), "tn_density_bwd_train")
     else:
         g_raw = _f32((n, 1), g_w.device)
-        _hip.check(lib.tn_density_act_bwd(t.raw.data_ptr(), 1, t.sel.data_ptr(), net_struct.average_init_density, exp_min,
+        _hip.check(lib.tn_density_act_bwd(t.raw.data_ptr(), 1, t.sel.data_ptr(), net_struct.average_init_density, opts.exp_min,
                                           g_density.data_ptr(), n, g_raw.data_ptr(), 1, 0, _stream()), "tn_density_act_bwd")
         H = t.hid.shape[1]
-        if chained:
-            linear_chain_bwd([(net_struct.l1, t.hid, 0, H, ACT_RELU, grads[names[3]], grads[names[4]]),
-                              (net_struct.l0, t.enc, 0, E, ACT_NONE, grads[names[1]], grads[names[2]])],
-                             None, ACT_NONE, g_raw, 1, n, g_enc, 0, E, False)
-        else:
-            g_hid = _f32((n, H), g_w.device)
-            linear_bwd(t.hid, 0, H, None, g_raw, 1, net_struct.l1, ACT_NONE, n, g_hid, 0, H, False, grads[names[3]], grads[names[4]])
-            linear_bwd(t.enc, 0, E, t.hid, g_hid, H, net_struct.l0, ACT_RELU, n, g_enc, 0, E, False, grads[names[1]], grads[names[2]])
-    hash_encode_bwd(net_struct.grid, net_struct.space, t.pos, g_enc, grads[names[0]], bucketed, spread, keep=keep)
+        linear_chain_bwd([(net_struct.l1, t.hid, 0, H, ACT_RELU, grads[names[3]], grads[names[4]]),
+                          (net_struct.l0, t.enc, 0, E, ACT_NONE, grads[names[1]], grads[names[2]])],
+                         None, ACT_NONE, g_raw, 1, n, g_enc, 0, E, False, opts.chained)
+    hash_encode_bwd(net_struct.grid, net_struct.space, t.pos, g_enc, grads[names[0]], opts.bucketed, opts.spread, keep=keep)
     if ray_grads is not None:
         _ray_grads_from_enc(net_struct.grid, net_struct.space, t, g_enc, *ray_grads, keep=keep)
+
+
+# ---- what the per-call backward and the step call's backward share --------------------------------------------------------------
+# tn_field_grads member prefix -> parameter name prefix of the field's Linear layers
+FIELD_LAYERS = {"base0": "field.mlp_base.mlp.layers.0", "base1": "field.mlp_base.mlp.layers.1",
+                "head0": "field.mlp_head.layers.0", "head1": "field.mlp_head.layers.1", "head2": "field.mlp_head.layers.2",
+                "th0": "field.mlp_thermal.layers.0", "th1": "field.mlp_thermal.layers.1", "thead": "field.field_head_thermal.net"}
+
+
+def _grad_view(arena: _GradArena, grads: Dict[str, Tensor], name: str) -> Tensor:
+    """the arena's zero-filled view for parameter ``name``, entered into the step's gradients"""
+    grads[name] = arena.get(name)
+    return grads[name]
+
+
+def _bind_field_grads(arena: _GradArena, grads: Dict[str, Tensor], want_rgb: bool, want_thermal: bool) -> "_hip.tn_field_grads":
+    """tn_field_grads over the arena's views; a head that no loss reaches keeps NULL members (and its parameters get no gradient)"""
+    gr = _hip.tn_field_grads()
+    for key, name in FIELD_LAYERS.items():
+        if (key.startswith("head") and not want_rgb) or (key.startswith("th") and not want_thermal):
+            continue
+        setattr(gr, key + "_w", _grad_view(arena, grads, name + ".weight").data_ptr())
+        if key != "head0":  # (mlp_head.0's bias comes from the ray-level part)
+            setattr(gr, key + "_b", _grad_view(arena, grads, name + ".bias").data_ptr())
+    return gr
+
+
+def _ray_grad_buffers(ctx, arena: _GradArena) -> Optional[Tuple[Tensor, Tensor]]:
+    """camera-pose optimisation: the ray origins / directions carry gradient (NS CameraOptimizer.apply_to_raybundle)"""
+    need = ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
+    return (arena.zeros(tuple(ctx.o.shape)), arena.zeros(tuple(ctx.d.shape))) if need else None
+
+
+def _grad_result(ctx, ray_grads: Optional[Tuple[Tensor, Tensor]], grads: Dict[str, Tensor]) -> tuple:
+    """RenderTrain.backward's return value: (model, origins, directions, 5 more inputs without gradient, *parameters)"""
+    g_o, g_d = ray_grads if ray_grads else (None, None)
+    return (None, g_o, g_d) + (None,) * 5 + tuple(grads.get(n) for n in ctx.param_names)
+
+
+# ---- what the forward keeps of the final level for its backward (besides the level's tape) -----------------------------------------
+# tape-free: tn_field_bwd_fused recomputes the hidden layers from enc / selector / density and these — ray_bias [R,64]: the per-ray
+# constant inputs of mlp_head.0 (SH(direction), appearance embedding) as a bias; base_out [N,16]: mlp_base's output rows
+# (opts.keep_base, else None); jacobian [N,96]: d hash features / d position (opts.keep_jac, else None)
+_TapeFreeActs = namedtuple("_TapeFreeActs", "ray_bias base_out jacobian rgb_s th_s")
+# taped: every layer's activated output in the layout the layer adjoints read — bo [N, 1 + geo]: raw density | geo features; cin: the
+# colour layer's input rows, which its weight gradient multiplies
+_TapedActs = namedtuple("_TapedActs", "h1 bo cin c1 c2 rgb_s t1 t2 th_s")
+
+
+def _proposal_fwd_taped(lib, prop_structs, o, d, nears, fars, jit, P, S, anneal, spacing_flags, opts):
+    """the proposal networks take gradient this step: sample -> taped density -> weights, level by level
+    -> (tapes, spacing and euclidean bins of the final level)"""
+    R, dev = o.shape[0], o.device
+    spacing, eucl = _f32((R, P[0] + 1), dev), _f32((R, P[0] + 1), dev)
+    _hip.check(lib.tn_sample_initial(linspace_bins(P[0], dev).data_ptr(), jit[0].data_ptr(), nears.data_ptr(), fars.data_ptr(), R, P[0],
+                                     spacing_flags, spacing.data_ptr(), eucl.data_ptr(), _stream()), "tn_sample_initial")
+    tapes: List[_LevelTape] = []
+    counts = (P[1], S)
+    for lvl in range(2):
+        t = _proposal_level_fwd(prop_structs[lvl], o, d, spacing, eucl, opts.fused_proposal)
+        tapes.append(t)
+        n_out = counts[lvl]
+        w_in = t.weights if anneal == 1.0 else torch.pow(t.weights, anneal)
+        spacing, eucl = _f32((R, n_out + 1), dev), _f32((R, n_out + 1), dev)
+        _hip.check(lib.tn_sample_pdf(w_in.data_ptr(), t.spacing.data_ptr(), pdf_positions(n_out + 1, dev, True).data_ptr(),
+                                     jit[lvl + 1].data_ptr(), nears.data_ptr(), fars.data_ptr(), R, P[lvl], n_out,
+                                     spacing_flags, spacing.data_ptr(), eucl.data_ptr(), _stream()), "tn_sample_pdf")
+    return tapes, spacing, eucl
+
+
+def _proposal_fwd_frozen(lib, model, prop_structs, rays, cam, jitter, P, S, single):
+    """nerfstudio evaluates the proposal densities under no_grad on these steps (5 of 6 after warm-up): no tape is needed, so both
+    levels run as ONE fused kernel (tn_proposal_sample_fwd, train-mode semantics)
+    -> (tapes with bins and weights only, the levels' depths, spacing and euclidean bins of the final level)"""
+    o = rays[0]
+    R, dev = o.shape[0], o.device
+    rc = render_config(model, True, per_sample_jitter=0 if single else 1)
+    ins = render_inputs(rc, dev, rays, cam, jitter)
+    outs = _hip.tn_render_outputs()
+    ns = (P[0], P[1], S)
+    sp = [_f32((R, k + 1), dev) for k in ns]
+    eu = [_f32((R, k + 1), dev) for k in ns]
+    ws_ = [_f32((R, k), dev) for k in ns[:2]]
+    prop_depths = [_f32((R, 1), dev), _f32((R, 1), dev)]
+    for i in range(3):
+        outs.spacing_bins[i], outs.eucl_bins[i] = sp[i].data_ptr(), eu[i].data_ptr()
+    outs.weights[0], outs.weights[1] = ws_[0].data_ptr(), ws_[1].data_ptr()
+    outs.prop_depth_0, outs.prop_depth_1 = prop_depths[0].data_ptr(), prop_depths[1].data_ptr()
+    need = lib.tn_render_workspace_bytes(rc, R)
+    wsb = torch.empty(need, dtype=torch.uint8, device=dev)
+    _hip.check(lib.tn_proposal_sample_fwd(prop_structs[0], prop_structs[1], rc, ins, outs, R, wsb.data_ptr(), need,
+                                          _stream()), "tn_proposal_sample_fwd")
+    tapes = [_LevelTape(), _LevelTape()]
+    for i, t in enumerate(tapes):
+        t.spacing, t.eucl, t.weights = sp[i], eu[i], ws_[i]
+    return tapes, prop_depths, sp[2], eu[2]
+
+
+def _field_fwd_tape_free(lib, fld, fused, f: _LevelTape, d, cam, R: int, S: int, opts: _StepOptions) -> _TapeFreeActs:
+    """the forward keeps enc / selector / density / rgb / thermal; tn_field_bwd_fused recomputes the rest"""
+    dev, N = d.device, R * S
+    ray_bias = _f32((R, 64), dev)
+    _hip.check(lib.tn_ray_head_fwd(fld, d.data_ptr(), cam.data_ptr(), R, ray_bias.data_ptr(), _stream()), "tn_ray_head_fwd")
+    f.enc, f.sel, f.density = _f32(((N + 63) // 64 * 64, 32), dev), _f32((N,), dev), _f32((N,), dev)  # enc: 64-sample tiles
+    rgb_s, th_s = _f32((N, 3), dev), _f32((N, 1), dev)
+    # (round 5) mlp_base's 16 output rows too, 64 B per sample: the backward's two head launches read them instead of
+    # recomputing mlp_base
+    base_out = _f32((N, 16), dev) if opts.keep_base else None
+    # (round 5) camera-pose optimisation: d hash features / d position while the corner values are in registers (384 B per
+    # sample) — the backward's position gradient then reads no table
+    jac = _f32(((N + 63) // 64 * 64, 96), dev) if opts.keep_jac else None
+    _hip.check(lib.tn_field_fwd_train(fused, f.pos.data_ptr(), ray_bias.data_ptr(), R, S, f.enc.data_ptr(), f.sel.data_ptr(),
+                                      f.density.data_ptr(), rgb_s.data_ptr(), th_s.data_ptr(), _hip.ptr(base_out),
+                                      _hip.ptr(jac), _stream()), "tn_field_fwd_train")
+    return _TapeFreeActs(ray_bias, base_out, jac, rgb_s, th_s)
+
+
+def _field_fwd_taped(lib, fld, fused, f: _LevelTape, d, cam, R: int, S: int) -> _TapedActs:
+    """the whole field forward of the level in one launch; every tensor of the tape in the layout the adjoints read"""
+    dev, N = d.device, R * S
+    f.enc, f.sel, f.density = _f32((N, 32), dev), _f32((N,), dev), _f32((N,), dev)
+    h1, bo = _f32((N, 64), dev), _f32((N, 16), dev)
+    c1, c2, rgb_s = _f32((N, 64), dev), _f32((N, 64), dev), _f32((N, 3), dev)
+    t1, t2, th_s = _f32((N, 64), dev), _f32((N, 64), dev), _f32((N, 1), dev)
+    _hip.check(lib.tn_field_fwd_taped(fused, f.pos.data_ptr(), d.data_ptr(), cam.data_ptr(), R, S, f.enc.data_ptr(),
+                                      f.sel.data_ptr(), h1.data_ptr(), bo.data_ptr(), f.density.data_ptr(),
+                                      c1.data_ptr(), c2.data_ptr(), rgb_s.data_ptr(), t1.data_ptr(), t2.data_ptr(),
+                                      th_s.data_ptr(), _stream()), "tn_field_fwd_taped")
+    cin = _f32((N, 64), dev)
+    _hip.check(lib.tn_color_input_fwd(fld, d.data_ptr(), bo.data_ptr() + 4, bo.shape[1], cam.data_ptr(), 1, R, S,
+                                      cin.data_ptr(), _stream()), "tn_color_input_fwd")
+    return _TapedActs(h1, bo, cin, c1, c2, rgb_s, t1, t2, th_s)
+
+
+def _field_fwd_staged(lib, fld, f: _LevelTape, d, cam, R: int, S: int) -> _TapedActs:
+    """one launch per nerfstudio module / layer (any layer width; also the cross-check of the fused forms)"""
+    dev, N = d.device, R * S
+    f.enc, f.sel = hash_encode_fwd(fld.grid, fld.space, f.pos)
+    h1 = linear_fwd(f.enc, 0, f.enc.shape[1], fld.base0, ACT_RELU, N)
+    bo = linear_fwd(h1, 0, h1.shape[1], fld.base1, ACT_NONE, N)
+    ldb = bo.shape[1]
+    f.density = _f32((N,), dev)
+    _hip.check(lib.tn_density_act_fwd(bo.data_ptr(), ldb, f.sel.data_ptr(), fld.average_init_density, N,
+                                      f.density.data_ptr(), _stream()), "tn_density_act_fwd")
+    cin = _f32((N, 64), dev)
+    _hip.check(lib.tn_color_input_fwd(fld, d.data_ptr(), bo.data_ptr() + 4, ldb, cam.data_ptr(), 1, R, S,
+                                      cin.data_ptr(), _stream()), "tn_color_input_fwd")
+    c1 = linear_fwd(cin, 0, 64, fld.head0, ACT_RELU, N)
+    c2 = linear_fwd(c1, 0, c1.shape[1], fld.head1, ACT_RELU, N)
+    rgb_s = linear_fwd(c2, 0, c2.shape[1], fld.head2, ACT_SIGMOID, N)
+    t1 = linear_fwd(bo, 1, ldb, fld.th0, ACT_RELU, N)
+    t2 = linear_fwd(t1, 0, t1.shape[1], fld.th1, ACT_SIGMOID, N)
+    th_s = linear_fwd(t2, 0, t2.shape[1], fld.thead, ACT_NONE, N)
+    return _TapedActs(h1, bo, cin, c1, c2, rgb_s, t1, t2, th_s)
 
 
 class RenderTrain(torch.autograd.Function):
@@ -435,150 +610,58 @@ class RenderTrain(torch.autograd.Function):
     def forward(ctx, model, o: Tensor, d: Tensor, nears: Tensor, fars: Tensor, cam: Tensor, jitter: Tensor,
                 updated: bool, *params: Tensor):
         lib = _hip.load()
-        ctx.set_materialize_grads(False)  # outputs no loss touches arrive as None: their branches are skipped
+        ctx.set_materialize_grads(False)  # outputs no loss touches arrive as None in backward (not as zero tensors): their branches are skipped
         cfg = model.config
         dev = o.device
         R = o.shape[0]
         P = tuple(cfg.num_proposal_samples_per_ray)
         S = cfg.num_nerf_samples_per_ray
+        opts = _step_options(model, cfg, R, S, o.requires_grad or d.requires_grad)
         # use_same_proposal_network: ONE HashMLPDensityField serves both levels [REF thermal_nerf_model.py:127-139]
         nets = len(model.proposal_networks)
         prop_structs = [model.proposal_networks[min(i, nets - 1)].train_struct() for i in range(2)]
         fld = model.field.train_struct()
-        anneal = float(model.proposal_sampler._anneal)
-        uniform = int(model.proposal_sampler.initial_sampler.uniform_spacing)  # REF thermal_nerf_model.py:164-170
         single = bool(cfg.use_single_jitter)  # REF thermal_nerf_model.py:176; False: one draw per bin edge
         jitter, jit = jitter_levels(jitter, R, (P[0], P[1], S), single)
-        spacing_flags = uniform | (0 if single else 2)
 
         # ---- proposal levels ---------------------------------------------------------------------------------
-        tapes: List[_LevelTape] = []
         prop_depths: List[Tensor] = []
         if updated:
-            # the proposal networks take gradient this step: sample -> taped density -> weights, level by level
-            spacing = _f32((R, P[0] + 1), dev)
-            eucl = _f32((R, P[0] + 1), dev)
-            _hip.check(lib.tn_sample_initial(linspace_bins(P[0], dev).data_ptr(), jit[0].data_ptr(), nears.data_ptr(),
-                                             fars.data_ptr(), R, P[0], spacing_flags, spacing.data_ptr(), eucl.data_ptr(),
-                                             _stream()),
-                       "tn_sample_initial")
-            counts = (P[1], S)
-            for lvl in range(2):
-                t = _proposal_level_fwd(prop_structs[lvl], o, d, spacing, eucl, bool(getattr(cfg, "fused_proposal_training", True)))
-                tapes.append(t)
-                n_out = counts[lvl]
-                w_in = t.weights if anneal == 1.0 else torch.pow(t.weights, anneal)
-                spacing, eucl = _f32((R, n_out + 1), dev), _f32((R, n_out + 1), dev)
-                _hip.check(lib.tn_sample_pdf(w_in.data_ptr(), t.spacing.data_ptr(), pdf_positions(n_out + 1, dev, True).data_ptr(),
-                                             jit[lvl + 1].data_ptr(), nears.data_ptr(), fars.data_ptr(), R, P[lvl], n_out,
-                                             spacing_flags, spacing.data_ptr(), eucl.data_ptr(), _stream()), "tn_sample_pdf")
+            uniform = int(model.proposal_sampler.initial_sampler.uniform_spacing)  # REF thermal_nerf_model.py:164-170
+            tapes, spacing, eucl = _proposal_fwd_taped(lib, prop_structs, o, d, nears, fars, jit, P, S, float(model.proposal_sampler._anneal),
+                                                       uniform | (0 if single else 2), opts)
+        elif opts.step_call:
+            # the whole forward chain of a step without proposal gradients as ONE C-ABI call (tn_train_step_fwd, round 6)
+            return _StepCall.forward(ctx, model, opts, o, d, nears, fars, cam, jitter, params, prop_structs, single)
         else:
-            # nerfstudio evaluates the proposal densities under no_grad on these steps (5 of 6 after warm-up): no tape is
-            # needed, so both levels run as ONE fused kernel (tn_proposal_sample_fwd, train-mode semantics)
-            if _step_call_applies(model, cfg):
-                # ... and the whole forward chain of such a step as ONE C-ABI call (tn_train_step_fwd, round 6)
-                return _StepCall.forward(ctx, model, o, d, nears, fars, cam, jitter, params, prop_structs, single)
-            rc = render_config(model, True, per_sample_jitter=0 if single else 1)
-            ins = render_inputs(rc, dev, (o, d, nears, fars), cam, jitter)
-            outs = _hip.tn_render_outputs()
-            ns = (P[0], P[1], S)
-            sp = [_f32((R, k + 1), dev) for k in ns]
-            eu = [_f32((R, k + 1), dev) for k in ns]
-            ws_ = [_f32((R, k), dev) for k in ns[:2]]
-            prop_depths = [_f32((R, 1), dev), _f32((R, 1), dev)]
-            for i in range(3):
-                outs.spacing_bins[i], outs.eucl_bins[i] = sp[i].data_ptr(), eu[i].data_ptr()
-            outs.weights[0], outs.weights[1] = ws_[0].data_ptr(), ws_[1].data_ptr()
-            outs.prop_depth_0, outs.prop_depth_1 = prop_depths[0].data_ptr(), prop_depths[1].data_ptr()
-            need = lib.tn_render_workspace_bytes(rc, R)
-            wsb = torch.empty(need, dtype=torch.uint8, device=dev)
-            _hip.check(lib.tn_proposal_sample_fwd(prop_structs[0], prop_structs[1], rc, ins, outs, R, wsb.data_ptr(), need,
-                                                  _stream()), "tn_proposal_sample_fwd")
-            for i in range(2):
-                t = _LevelTape()
-                t.spacing, t.eucl, t.weights = sp[i], eu[i], ws_[i]
-                tapes.append(t)
-            spacing, eucl = sp[2], eu[2]
+            tapes, prop_depths, spacing, eucl = _proposal_fwd_frozen(lib, model, prop_structs, (o, d, nears, fars), cam, jitter, P, S, single)
 
-        # ---- final level: taped field ----------------------------------------------------------------------
+        # ---- final level: the field in one of its three forms -----------------------------------------------
         f = _LevelTape()
         f.spacing, f.eucl = spacing, eucl
         f.pos, f.deltas = _frustum_positions(o, d, f)
-        N = R * S
         fused = None
-        tape_free = bool(getattr(cfg, "tape_free_training", True))
-        if cfg.fused_train_forward or tape_free:
+        if opts.fused_forward or opts.tape_free:
             # MFMA fragments of the CURRENT weights (rebuilt per step); None: geometry the MFMA chain does not cover -> the
-            # stage-by-stage entry points below
+            # stage-by-stage entry points
             fused = model.field.train_struct(prepare=True)
-        tape_free = tape_free and fused is not None
         # config.deferred_table_update: the previous step's table scatter + Adam may still be running on the side streams; everything
         # above (camera optimizer, proposal pass, level geometry, field_prepare) needed neither — the field's table reads do
         _hip.join_pending(dev)
-        h1 = bo = cin = c1 = c2 = t1 = t2 = None
-        if tape_free:
-            # no activation tape: the per-ray constant inputs of mlp_head.0 (SH(direction), appearance embedding) become a
-            # per-ray bias [R,64]; the forward keeps enc / selector / density / rgb / thermal, tn_field_bwd_fused recomputes the rest
-            ray_bias = _f32((R, 64), dev)
-            _hip.check(lib.tn_ray_head_fwd(fld, d.data_ptr(), cam.data_ptr(), R, ray_bias.data_ptr(), _stream()), "tn_ray_head_fwd")
-            f.enc, f.sel, f.density = _f32(((N + 63) // 64 * 64, 32), dev), _f32((N,), dev), _f32((N,), dev)  # enc: 64-sample tiles
-            rgb_s, th_s = _f32((N, 3), dev), _f32((N, 1), dev)
-            # (round 5) mlp_base's 16 output rows too, 64 B per sample: the backward's two head launches read them instead of
-            # recomputing mlp_base (the split form only: the one-launch form needs the hidden layer anyway)
-            keep_base = bool(getattr(cfg, "store_base_output", True)) and bool(getattr(cfg, "fused_backward_split", True))
-            base_out = _f32((N, 16), dev) if keep_base else None
-            # (round 5) camera-pose optimisation: d hash features / d position while the corner values are in registers (384 B per
-            # sample) — the backward's position gradient then reads no table
-            keep_jac = (o.requires_grad or d.requires_grad) and bool(getattr(cfg, "store_position_jacobian", True)) \
-                and bool(getattr(cfg, "fused_backward_split", True))
-            jac = _f32(((N + 63) // 64 * 64, 96), dev) if keep_jac else None
-            _hip.check(lib.tn_field_fwd_train(fused, f.pos.data_ptr(), ray_bias.data_ptr(), R, S, f.enc.data_ptr(), f.sel.data_ptr(),
-                                              f.density.data_ptr(), rgb_s.data_ptr(), th_s.data_ptr(), _hip.ptr(base_out),
-                                              _hip.ptr(jac), _stream()),
-                       "tn_field_fwd_train")
-            bo = ray_bias  # (slot reuse in ctx.acts: the tape-free backward reads (ray_bias, rgb_s) ...
-            h1 = base_out  # ... mlp_base's output rows, if kept ...
-            cin = jac      # ... and the position Jacobian, if kept)
-        elif fused is not None and cfg.fused_train_forward:
-            # the whole field forward of the level in one launch; every tensor of the tape in the layout the adjoints read
-            f.enc, f.sel, f.density = _f32((N, 32), dev), _f32((N,), dev), _f32((N,), dev)
-            h1, bo = _f32((N, 64), dev), _f32((N, 16), dev)
-            c1, c2, rgb_s = _f32((N, 64), dev), _f32((N, 64), dev), _f32((N, 3), dev)
-            t1, t2, th_s = _f32((N, 64), dev), _f32((N, 64), dev), _f32((N, 1), dev)
-            _hip.check(lib.tn_field_fwd_taped(fused, f.pos.data_ptr(), d.data_ptr(), cam.data_ptr(), R, S, f.enc.data_ptr(),
-                                              f.sel.data_ptr(), h1.data_ptr(), bo.data_ptr(), f.density.data_ptr(),
-                                              c1.data_ptr(), c2.data_ptr(), rgb_s.data_ptr(), t1.data_ptr(), t2.data_ptr(),
-                                              th_s.data_ptr(), _stream()), "tn_field_fwd_taped")
-            ldb = bo.shape[1]
-            cin = _f32((N, 64), dev)  # the colour layer's input rows, which its weight gradient multiplies
-            _hip.check(lib.tn_color_input_fwd(fld, d.data_ptr(), bo.data_ptr() + 4, ldb, cam.data_ptr(), 1, R, S,
-                                              cin.data_ptr(), _stream()), "tn_color_input_fwd")
+        if opts.tape_free and fused is not None:
+            acts = _field_fwd_tape_free(lib, fld, fused, f, d, cam, R, S, opts)
+        elif opts.fused_forward and fused is not None:
+            acts = _field_fwd_taped(lib, fld, fused, f, d, cam, R, S)
         else:
-            f.enc, f.sel = hash_encode_fwd(fld.grid, fld.space, f.pos)
-            E = f.enc.shape[1]
-            h1 = linear_fwd(f.enc, 0, E, fld.base0, ACT_RELU, N)
-            bo = linear_fwd(h1, 0, h1.shape[1], fld.base1, ACT_NONE, N)  # [N, 1 + geo]: raw density | geo features
-            ldb = bo.shape[1]
-            f.density = _f32((N,), dev)
-            _hip.check(lib.tn_density_act_fwd(bo.data_ptr(), ldb, f.sel.data_ptr(), fld.average_init_density, N,
-                                              f.density.data_ptr(), _stream()), "tn_density_act_fwd")
-            cin = _f32((N, 64), dev)
-            _hip.check(lib.tn_color_input_fwd(fld, d.data_ptr(), bo.data_ptr() + 4, ldb, cam.data_ptr(), 1, R, S,
-                                              cin.data_ptr(), _stream()), "tn_color_input_fwd")
-            c1 = linear_fwd(cin, 0, 64, fld.head0, ACT_RELU, N)
-            c2 = linear_fwd(c1, 0, c1.shape[1], fld.head1, ACT_RELU, N)
-            rgb_s = linear_fwd(c2, 0, c2.shape[1], fld.head2, ACT_SIGMOID, N)
-            t1 = linear_fwd(bo, 1, ldb, fld.th0, ACT_RELU, N)
-            t2 = linear_fwd(t1, 0, t1.shape[1], fld.th1, ACT_SIGMOID, N)
-            th_s = linear_fwd(t2, 0, t2.shape[1], fld.thead, ACT_NONE, N)
+            acts = _field_fwd_staged(lib, fld, f, d, cam, R, S)
         # get_weights + the RGB / thermal / accumulation renderers of the level: one launch (tn_ray_render_fwd)
         f.weights = _f32((R, S), dev)
         rgb, thermal, acc = _f32((R, 3), dev), _f32((R, 1), dev), _f32((R, 1), dev)
-        _hip.check(lib.tn_ray_render_fwd(f.deltas.data_ptr(), f.density.data_ptr(), rgb_s.data_ptr(), th_s.data_ptr(), R, S,
+        _hip.check(lib.tn_ray_render_fwd(f.deltas.data_ptr(), f.density.data_ptr(), acts.rgb_s.data_ptr(), acts.th_s.data_ptr(), R, S,
                                          f.weights.data_ptr(), rgb.data_ptr(), thermal.data_ptr(), acc.data_ptr(), _stream()),
                    "tn_ray_render_fwd")
         # the step's regularisers start now, beside the depth renderers (config.overlap_regularisers)
-        _precompute_regularisers(model, [t.weights for t in tapes] + [f.weights], [t.spacing for t in tapes] + [f.spacing])
+        _precompute_regularisers(model, opts, [t.weights for t in tapes] + [f.weights], [t.spacing for t in tapes] + [f.spacing])
         depth, expected = _f32((R, 1), dev), _f32((R, 1), dev)
         scratch = _f32((2,), dev)
         starts, ends = _starts_ends(f)
@@ -591,12 +674,9 @@ class RenderTrain(torch.autograd.Function):
                                         pd.data_ptr(), None, None, _stream()), "tn_depth_fwd")
             prop_depths.append(pd)
 
-        ctx.set_materialize_grads(False)  # outputs nobody differentiates arrive as None in backward, not as zero tensors
-        ctx.model, ctx.tapes, ctx.field_tape = model, tapes, f
-        ctx.acts = (h1, bo, cin, c1, c2, rgb_s, t1, t2, th_s)
+        ctx.model, ctx.tapes, ctx.field_tape, ctx.acts = model, tapes, f, acts
         ctx.acc, ctx.o, ctx.d, ctx.cam = acc, o, d, cam
         ctx.updated = bool(updated)
-        ctx.tape_free = tape_free
         ctx.param_names = model.named_parameter_lists()[0]
         ctx.params = dict(zip(ctx.param_names, params))
         # ctx must not hold a tensor OBJECT that is also returned as a differentiable output (output -> grad_fn -> ctx ->
@@ -613,223 +693,182 @@ class RenderTrain(torch.autograd.Function):
     def backward(ctx, g_rgb, g_th, g_acc, g_w0, g_w1, g_w2, *unused):
         if getattr(ctx, "step_call", None) is not None:
             return _StepCall.backward(ctx, g_rgb, g_th, g_acc, g_w2)
-        lib = _hip.load()
-        model, f = ctx.model, ctx.field_tape
-        cfg = model.config
+        model, f, acts = ctx.model, ctx.field_tape, ctx.acts
         dev = ctx.o.device
         _drop_precomputed((dev, _hip.current_stream()))  # side-stream regularisers of this forward that no loss collected
-        h1, bo, cin, c1, c2, rgb_s, t1, t2, th_s = ctx.acts
         R, S = f.weights.shape
-        N = R * S
-        fld = model.field.train_struct()
-        like = ctx.params
+        arena = _GradArena(ctx.params, dev, R, S)  # every gradient buffer of this step: one allocation, one fill
         grads: Dict[str, Tensor] = {}
-        # camera-pose optimisation: the ray origins / directions carry gradient (NS CameraOptimizer.apply_to_raybundle)
-        ray_grads = None
-        R_, S_ = f.weights.shape
-        arena = _GradArena(like, dev, extra=R_ * (64 + 2 * 64 + S_) + 1024)  # every gradient buffer of this step: one allocation, one fill
-        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
-            ray_grads = (arena.zeros(tuple(ctx.o.shape)), arena.zeros(tuple(ctx.d.shape)))
+        ray_grads = _ray_grad_buffers(ctx, arena)
+        # (this path has always read config.bucketed_table_scatter as a flag: an int means "on" here, at the level the library
+        # advises; only the step call and hash_encode_bwd itself take the level)
+        opts = _step_options(model, model.config, R, S, ray_grads is not None)
+        opts = replace(opts, bucketed=bool(opts.bucketed))
         # NS SHEncoding.pytorch_fwd is @torch.no_grad(): by default the SH basis passes no gradient to the
         # directions; config.sh_direction_gradient=True adds that term (a differentiable SH encoding)
-        sh_grads = ray_grads is not None and bool(cfg.sh_direction_gradient)
+        sh_grads = ray_grads is not None and bool(model.config.sh_direction_gradient)
+        g_prop, prop_join = RenderTrain._proposal_levels_beside(ctx, opts, grads, arena, ray_grads, (g_w0, g_w1))
+        g_rgb_s, g_th_s, g_density = RenderTrain._render_bwd(ctx, g_rgb, g_th, g_acc, g_w2)
+        g_enc = _f32((R * S, f.enc.shape[1]), dev)  # row-major [N,32] in both forms (what the table scatter reads)
+        field_bwd = _field_bwd_tape_free if isinstance(acts, _TapeFreeActs) else _field_bwd_taped
+        field_bwd(ctx, opts, arena, grads, ray_grads, sh_grads, g_rgb_s, g_th_s, g_density, g_enc, can_defer=prop_join is None)
+        # the proposal levels, unless they are already queued on the third stream (then: the join)
+        if ctx.updated:
+            RenderTrain._proposal_levels(ctx, opts, grads, arena, ray_grads, g_prop)
+        if prop_join is not None:
+            third, ray_p, keep = prop_join
+            _step_streams(dev)[0].wait_stream(third)
+            if ray_grads and ray_p:
+                ray_grads[0].add_(ray_p[0])
+                ray_grads[1].add_(ray_p[1])
+            keep.clear()
+        result = _grad_result(ctx, ray_grads, grads)
+        ctx.tapes = ctx.field_tape = ctx.acts = ctx.acc = None  # the tape is dead after one backward
+        return result
 
-        def zeros(name: str) -> Tensor:
-            grads[name] = arena.get(name)
-            return grads[name]
-
-        chained = bool(cfg.fused_train_backward)  # each MLP's layers in ONE launch (tn_linear_chain_bwd) vs one launch per layer
-        bucketed = bool(getattr(cfg, "bucketed_table_scatter", True))
-        spread = bool(getattr(cfg, "spread_coarse_scatter", True))
-        exp_min = float(getattr(cfg, "trunc_exp_clamp_min", -15.0))
-        # ---- proposal levels, update steps (1 in 6 after warm-up) ---------------------------------------------------
-        # Their chain (get_weights adjoint -> density MLP -> the proposal grids' scatter -> positions) shares nothing with the final
-        # level's but the ray gradients: queued on the step's third stream it runs beside the MFMA-bound field backward (its own
-        # ray-gradient buffers, added at the join).  Only the fused forms qualify: the stage chain issues torch ops.
-        prop_join = None
-        g_prop = (g_w0, g_w1)
-        if ctx.updated and any(g is not None for g in g_prop):
-            fused_levels = all(t.hid is None for t in ctx.tapes)
-            if fused_levels and getattr(cfg, "overlap_table_scatter", True):
-                main, _, third = _step_streams(dev)
-                ray_p = (arena.zeros(tuple(ctx.o.shape)), arena.zeros(tuple(ctx.d.shape))) if ray_grads else None
-                gs = [None if g is None else g.reshape(t.weights.shape).contiguous() for g, t in zip(g_prop, ctx.tapes)]
-                keep: list = []
-                third.wait_stream(main)  # the cleared arena and the interlevel gradients are the main stream's work so far
-                _STREAM_OVERRIDE[0] = third.cuda_stream  # launches and allocations only until it is cleared
-                try:
-                    RenderTrain._proposal_levels(ctx, model, grads, arena, ray_p, chained, bucketed, exp_min, gs, keep)
-                finally:
-                    _STREAM_OVERRIDE[0] = None
-                prop_join = (third, ray_p, keep)
-                g_prop = (None, None)
-
-        # ---- final level ------------------------------------------------------------------------------------
-        # adjoints of the level's renderers and of get_weights (+ use_gradient_scaling, REF :228-231): one launch
+    @staticmethod
+    def _render_bwd(ctx, g_rgb, g_th, g_acc, g_w2):
+        """adjoints of the level's renderers and of get_weights (+ use_gradient_scaling, REF :228-231): one launch
+        -> gradients of the samples' rgb (or None), thermal (or None) and density"""
+        f, acts, dev = ctx.field_tape, ctx.acts, ctx.o.device
+        R, S = f.weights.shape
+        N = R * S
         g_rgb_s = _f32((N, 3), dev) if g_rgb is not None else None
         g_th_s = _f32((N, 1), dev) if g_th is not None else None
         g_density = _f32((R, S), dev)
         g_wx = None if g_w2 is None else _hip.require_device_tensor(g_w2.reshape(R, S), "d weights")
-        st_en = _starts_ends(f) if cfg.use_gradient_scaling else (None, None)
-        _hip.check(lib.tn_ray_render_bwd(f.deltas.data_ptr(), f.density.data_ptr(), rgb_s.data_ptr(), th_s.data_ptr(),
-                                         ctx.acc.data_ptr(), _hip.ptr(None if g_rgb is None else g_rgb.contiguous()),
-                                         _hip.ptr(None if g_th is None else g_th.contiguous()),
-                                         _hip.ptr(None if g_acc is None else g_acc.contiguous()), _hip.ptr(g_wx),
-                                         _hip.ptr(st_en[0]), _hip.ptr(st_en[1]), R, S, _hip.ptr(g_rgb_s), _hip.ptr(g_th_s),
-                                         g_density.data_ptr(), _stream()), "tn_ray_render_bwd")
-        E = f.enc.shape[1]
-        g_enc = _f32((N, E), dev)  # row-major [N,32] in both forms (what the table scatter reads)
-        if ctx.tape_free:
-            self_bias = bo  # ray_bias [R,64]
-            gr = _hip.tn_field_grads()
-            names = {"base0": "field.mlp_base.mlp.layers.0", "base1": "field.mlp_base.mlp.layers.1",
-                     "head0": "field.mlp_head.layers.0", "head1": "field.mlp_head.layers.1", "head2": "field.mlp_head.layers.2",
-                     "th0": "field.mlp_thermal.layers.0", "th1": "field.mlp_thermal.layers.1", "thead": "field.field_head_thermal.net"}
-            for key, name in names.items():
-                if key.startswith("head") and g_rgb_s is None:
-                    continue
-                if key.startswith("th") and g_th_s is None:
-                    continue
-                setattr(gr, key + "_w", zeros(name + ".weight").data_ptr())
-                if key != "head0":
-                    setattr(gr, key + "_b", zeros(name + ".bias").data_ptr())
-            g_ray = arena.zeros((R, 64)) if g_rgb_s is not None else None
-            ws = _fused_bwd_workspace(dev, R, S)
-            # 0: one launch; 1: colour head | thermal head | mlp_base; 2: the same with the heads' 64 x 64 products as bf16 pieces
-            split_form = 0 if not getattr(cfg, "fused_backward_split", True) else (2 if getattr(cfg, "backward_bf16_pieces", True) else 1)
-            g_pos = _f32((N, 3), dev) if ray_grads else None  # d loss / d sample position, written by the mlp_base launch
-            _hip.check(lib.tn_field_bwd_fused(fld, R, S, f.enc.data_ptr(), f.sel.data_ptr(), _hip.ptr(h1), self_bias.data_ptr(), rgb_s.data_ptr(),
-                                              _hip.ptr(g_rgb_s), _hip.ptr(g_th_s), g_density.data_ptr(),
-                                              1 if model.field.pass_thermal_gradients else 0, exp_min,
-                                              split_form, g_enc.data_ptr(),
-                                              _hip.ptr(g_ray), f.pos.data_ptr() if ray_grads else None, _hip.ptr(cin), _hip.ptr(g_pos),
-                                              C.byref(gr), ws.data_ptr(), ws.numel(), _stream()),
-                       "tn_field_bwd_fused")
-            zeros("field.mlp_base.encoder.hash_table")
-            if g_ray is not None:
-                for name in ("field.mlp_head.layers.0.bias", "field.embedding_appearance.embedding.weight"):
-                    zeros(name)
-            g_cin = _f32((R, 64), dev) if g_ray is not None and sh_grads else None
-
-            def ray_level_adjoints() -> None:  # nothing here touches the table gradient: queued beside its scatter
-                if g_ray is not None:
-                    # mlp_head.0's ray-level part: bias, SH and appearance weight columns, the embedding gradient
-                    _hip.check(lib.tn_ray_head_bwd(fld, ctx.d.data_ptr(), ctx.cam.data_ptr(), R, g_ray.data_ptr(),
-                                                   grads["field.mlp_head.layers.0.weight"].data_ptr(),
-                                                   grads["field.mlp_head.layers.0.bias"].data_ptr(),
-                                                   grads["field.embedding_appearance.embedding.weight"].data_ptr(), _hip.ptr(g_cin),
-                                                   _stream()), "tn_ray_head_bwd")
-                    if sh_grads:  # ... and on through the SH basis to the directions (camera-pose optimisation, differentiable-SH switch)
-                        _hip.check(lib.tn_color_input_bwd(fld, g_cin.data_ptr(), ctx.cam.data_ptr(), 1, R, 1, None, 0, None,
-                                                          ctx.d.data_ptr(), ray_grads[1].data_ptr(), _stream()), "tn_color_input_bwd")
-                if ray_grads:
-                    starts, ends = _starts_ends(f)
-                    _hip.check(lib.tn_frustum_positions_bwd(g_pos.data_ptr(), starts.data_ptr(), ends.data_ptr(), R, S,
-                                                            ray_grads[0].data_ptr(), ray_grads[1].data_ptr(), _stream()),
-                               "tn_frustum_positions_bwd")
-
-            # config.deferred_table_update: both halves on side streams, not joined here (steps whose third stream carries the
-            # proposal levels' backward keep the joined form: that chain and the atomic half would queue behind one another)
-            defer = bool(getattr(cfg, "deferred_table_update", False)) and prop_join is None
-            if hash_encode_bwd(fld.grid, fld.space, f.pos, g_enc, grads["field.mlp_base.encoder.hash_table"], bucketed, spread,
-                               getattr(cfg, "overlap_table_scatter", True), ray_level_adjoints, defer=defer):
-                _hip.defer(dev, (), [arena.flat, f.enc, g_density, g_rgb_s, g_th_s])
-            return RenderTrain._finish(ctx, model, grads, arena, ray_grads, chained, bucketed, exp_min, g_prop, prop_join)
-        ldb = bo.shape[1]
-        # layer widths as built (config.hidden_dim / hidden_dim_color / hidden_dim_transient; 64 in the reference's configs)
-        Wb, Wc = h1.shape[1], c1.shape[1]
-        Wt1, Wt2 = t1.shape[1], t2.shape[1]
-        if model.field.staged:
-            chained = False  # (the chained launch tiles 64-wide layers)
-        g_bo = _f32((N, ldb), dev)  # column 0 written, the geo columns cleared (the += target of both heads) in one pass
-        _hip.check(lib.tn_density_act_bwd(bo.data_ptr(), ldb, f.sel.data_ptr(), fld.average_init_density, exp_min,
-                                          g_density.data_ptr(), N, g_bo.data_ptr(), ldb, ldb, _stream()), "tn_density_act_bwd")
-        if g_th_s is not None:  # thermal branch [REF thermal_field.py:170-179]
-            into_geo = g_bo if model.field.pass_thermal_gradients else None  # REF :171-172 (.detach())
-            th = [(fld.thead, t2, 0, Wt2, ACT_SIGMOID, zeros("field.field_head_thermal.net.weight"),
-                   zeros("field.field_head_thermal.net.bias")),
-                  (fld.th1, t1, 0, Wt1, ACT_RELU, zeros("field.mlp_thermal.layers.1.weight"), zeros("field.mlp_thermal.layers.1.bias")),
-                  (fld.th0, bo, 1, ldb, ACT_NONE, zeros("field.mlp_thermal.layers.0.weight"), zeros("field.mlp_thermal.layers.0.bias"))]
-            if chained:
-                linear_chain_bwd(th, None, ACT_NONE, g_th_s, 1, N, into_geo, 1, ldb, True)
-            else:
-                g_t2, g_t1 = _f32((N, Wt2), dev), _f32((N, Wt1), dev)
-                linear_bwd(t2, 0, Wt2, None, g_th_s, 1, fld.thead, ACT_NONE, N, g_t2, 0, Wt2, False, th[0][5], th[0][6])
-                linear_bwd(t1, 0, Wt1, t2, g_t2, Wt2, fld.th1, ACT_SIGMOID, N, g_t1, 0, Wt1, False, th[1][5], th[1][6])
-                linear_bwd(bo, 1, ldb, t1, g_t1, Wt1, fld.th0, ACT_RELU, N, into_geo, 1, ldb, True, th[2][5], th[2][6])
-        if g_rgb_s is not None:  # colour branch [REF :160-168]
-            g_cin = _f32((N, 64), dev)
-            hd = [(fld.head2, c2, 0, Wc, ACT_RELU, zeros("field.mlp_head.layers.2.weight"), zeros("field.mlp_head.layers.2.bias")),
-                  (fld.head1, c1, 0, Wc, ACT_RELU, zeros("field.mlp_head.layers.1.weight"), zeros("field.mlp_head.layers.1.bias")),
-                  (fld.head0, cin, 0, 64, ACT_NONE, zeros("field.mlp_head.layers.0.weight"), zeros("field.mlp_head.layers.0.bias"))]
-            if chained:
-                linear_chain_bwd(hd, rgb_s, ACT_SIGMOID, g_rgb_s, 3, N, g_cin, 0, 64, False)
-            else:
-                g_c2, g_c1 = _f32((N, Wc), dev), _f32((N, Wc), dev)
-                linear_bwd(c2, 0, Wc, rgb_s, g_rgb_s, 3, fld.head2, ACT_SIGMOID, N, g_c2, 0, Wc, False, hd[0][5], hd[0][6])
-                linear_bwd(c1, 0, Wc, c2, g_c2, Wc, fld.head1, ACT_RELU, N, g_c1, 0, Wc, False, hd[1][5], hd[1][6])
-                linear_bwd(cin, 0, 64, c1, g_c1, Wc, fld.head0, ACT_RELU, N, g_cin, 0, 64, False, hd[2][5], hd[2][6])
-            _hip.check(lib.tn_color_input_bwd(fld, g_cin.data_ptr(), ctx.cam.data_ptr(), 1, R, S, g_bo.data_ptr() + 4, ldb,
-                                              zeros("field.embedding_appearance.embedding.weight").data_ptr(),
-                                              ctx.d.data_ptr() if sh_grads else None,
-                                              ray_grads[1].data_ptr() if sh_grads else None, _stream()),
-                       "tn_color_input_bwd")
-        bs = [(fld.base1, h1, 0, Wb, ACT_RELU, zeros("field.mlp_base.mlp.layers.1.weight"), zeros("field.mlp_base.mlp.layers.1.bias")),
-              (fld.base0, f.enc, 0, E, ACT_NONE, zeros("field.mlp_base.mlp.layers.0.weight"), zeros("field.mlp_base.mlp.layers.0.bias"))]
-        if chained:
-            linear_chain_bwd(bs, None, ACT_NONE, g_bo, ldb, N, g_enc, 0, E, False)
-        else:
-            g_h1 = _f32((N, Wb), dev)
-            linear_bwd(h1, 0, Wb, None, g_bo, ldb, fld.base1, ACT_NONE, N, g_h1, 0, Wb, False, bs[0][5], bs[0][6])
-            linear_bwd(f.enc, 0, E, h1, g_h1, Wb, fld.base0, ACT_RELU, N, g_enc, 0, E, False, bs[1][5], bs[1][6])
-        hash_encode_bwd(fld.grid, fld.space, f.pos, g_enc, zeros("field.mlp_base.encoder.hash_table"), bucketed, spread,
-                        getattr(cfg, "overlap_table_scatter", True))
-        if ray_grads:
-            _ray_grads_from_enc(fld.grid, fld.space, f, g_enc, *ray_grads)
-        return RenderTrain._finish(ctx, model, grads, arena, ray_grads, chained, bucketed, exp_min, g_prop, prop_join)
+        st_en = _starts_ends(f) if ctx.model.config.use_gradient_scaling else (None, None)
+        _hip.check(_hip.load().tn_ray_render_bwd(
+            f.deltas.data_ptr(), f.density.data_ptr(), acts.rgb_s.data_ptr(), acts.th_s.data_ptr(), ctx.acc.data_ptr(),
+            _hip.ptr(None if g_rgb is None else g_rgb.contiguous()), _hip.ptr(None if g_th is None else g_th.contiguous()),
+            _hip.ptr(None if g_acc is None else g_acc.contiguous()), _hip.ptr(g_wx), _hip.ptr(st_en[0]), _hip.ptr(st_en[1]), R, S,
+            _hip.ptr(g_rgb_s), _hip.ptr(g_th_s), g_density.data_ptr(), _stream()), "tn_ray_render_bwd")
+        return g_rgb_s, g_th_s, g_density
 
     @staticmethod
-    def _proposal_levels(ctx, model, grads, arena, ray_grads, chained, bucketed, exp_min, g_prop, keep=None) -> None:
+    def _proposal_levels_beside(ctx, opts, grads, arena, ray_grads, g_prop):
+        """The proposal levels' backward of an update step (1 in 6 after warm-up) on the step's third stream.  Their chain
+        (get_weights adjoint -> density MLP -> the proposal grids' scatter -> positions) shares nothing with the final level's but the
+        ray gradients: queued there it runs beside the MFMA-bound field backward (its own ray-gradient buffers, added at the join).
+        Only the fused forms qualify: the stage chain issues torch ops.  -> (the level gradients still to do, what the backward joins at its end)"""
+        if not (ctx.updated and any(g is not None for g in g_prop) and opts.overlap and all(t.hid is None for t in ctx.tapes)):
+            return g_prop, None
+        main, _, third = _step_streams(ctx.o.device)
+        ray_p = _ray_grad_buffers(ctx, arena)
+        gs = [None if g is None else g.reshape(t.weights.shape).contiguous() for g, t in zip(g_prop, ctx.tapes)]
+        keep: list = []
+        third.wait_stream(main)  # the cleared arena and the interlevel gradients are the main stream's work so far
+        _STREAM_OVERRIDE.handle = third.cuda_stream  # launches and allocations only until it is cleared
+        try:
+            RenderTrain._proposal_levels(ctx, opts, grads, arena, ray_p, gs, keep)
+        finally:
+            _STREAM_OVERRIDE.handle = None
+        return (None, None), (third, ray_p, keep)
+
+    @staticmethod
+    def _proposal_levels(ctx, opts, grads, arena, ray_grads, g_prop, keep=None) -> None:
         """backward of the proposal levels (they receive gradient only through their weights: the interlevel loss)"""
+        model = ctx.model
         for lvl, g in enumerate(g_prop):
             if g is None:
                 continue
             t = ctx.tapes[lvl]
             which = min(lvl, len(model.proposal_networks) - 1)  # one shared network: both levels accumulate into it
             net = model.proposal_networks[which].train_struct()
-            _proposal_level_bwd(net, t, g.reshape(t.weights.shape).contiguous(), grads, f"proposal_networks.{which}", arena,
-                                ray_grads, chained, bucketed, exp_min, bool(getattr(model.config, "spread_coarse_scatter", True)), keep)
+            _proposal_level_bwd(net, t, g.reshape(t.weights.shape).contiguous(), grads, f"proposal_networks.{which}", arena, opts,
+                                ray_grads, keep)
 
-    @staticmethod
-    def _finish(ctx, model, grads, arena, ray_grads, chained, bucketed, exp_min, g_prop, prop_join=None):
-        """proposal levels unless they are already queued on the third stream (then: the join), then the gradient tuple in
-        parameter order"""
-        if ctx.updated:
-            RenderTrain._proposal_levels(ctx, model, grads, arena, ray_grads, chained, bucketed, exp_min, g_prop)
-        if prop_join is not None:
-            third, ray_p, keep = prop_join
-            _step_streams(ctx.o.device)[0].wait_stream(third)
-            if ray_grads and ray_p:
-                ray_grads[0].add_(ray_p[0])
-                ray_grads[1].add_(ray_p[1])
-            keep.clear()
 
-        g_o, g_d = ray_grads if ray_grads else (None, None)
-        result = (None, g_o, g_d) + (None,) * 5 + tuple(grads.get(n) for n in ctx.param_names)
-        ctx.tapes = ctx.field_tape = ctx.acts = ctx.acc = None  # the tape is dead after one backward
-        return result
+def _field_bwd_tape_free(ctx, opts, arena, grads, ray_grads, sh_grads, g_rgb_s, g_th_s, g_density, g_enc, can_defer: bool) -> None:
+    """the field's backward without a tape: tn_field_bwd_fused (the hidden layers recomputed), then the table scatter with the step's
+    ray-level adjoints queued beside it"""
+    lib = _hip.load()
+    model, f, acts, dev = ctx.model, ctx.field_tape, ctx.acts, ctx.o.device
+    R, S = f.weights.shape
+    N = R * S
+    fld = model.field.train_struct()
+    gr = _bind_field_grads(arena, grads, g_rgb_s is not None, g_th_s is not None)
+    g_ray = arena.zeros((R, 64)) if g_rgb_s is not None else None
+    ws = _fused_bwd_workspace(dev, R, S)
+    g_pos = _f32((N, 3), dev) if ray_grads else None  # d loss / d sample position, written by the mlp_base launch
+    _hip.check(lib.tn_field_bwd_fused(fld, R, S, f.enc.data_ptr(), f.sel.data_ptr(), _hip.ptr(acts.base_out), acts.ray_bias.data_ptr(),
+                                      acts.rgb_s.data_ptr(), _hip.ptr(g_rgb_s), _hip.ptr(g_th_s), g_density.data_ptr(),
+                                      1 if model.field.pass_thermal_gradients else 0, opts.exp_min, opts.split_form, g_enc.data_ptr(),
+                                      _hip.ptr(g_ray), f.pos.data_ptr() if ray_grads else None, _hip.ptr(acts.jacobian), _hip.ptr(g_pos),
+                                      C.byref(gr), ws.data_ptr(), ws.numel(), _stream()),
+               "tn_field_bwd_fused")
+    d_table = _grad_view(arena, grads, "field.mlp_base.encoder.hash_table")
+    if g_ray is not None:
+        for name in ("field.mlp_head.layers.0.bias", "field.embedding_appearance.embedding.weight"):
+            _grad_view(arena, grads, name)
+    g_cin = _f32((R, 64), dev) if g_ray is not None and sh_grads else None
+
+    def ray_level_adjoints() -> None:  # nothing here touches the table gradient: queued beside its scatter
+        if g_ray is not None:
+            # mlp_head.0's ray-level part: bias, SH and appearance weight columns, the embedding gradient
+            _hip.check(lib.tn_ray_head_bwd(fld, ctx.d.data_ptr(), ctx.cam.data_ptr(), R, g_ray.data_ptr(),
+                                           grads["field.mlp_head.layers.0.weight"].data_ptr(),
+                                           grads["field.mlp_head.layers.0.bias"].data_ptr(),
+                                           grads["field.embedding_appearance.embedding.weight"].data_ptr(), _hip.ptr(g_cin),
+                                           _stream()), "tn_ray_head_bwd")
+            if sh_grads:  # ... and on through the SH basis to the directions (camera-pose optimisation, differentiable-SH switch)
+                _hip.check(lib.tn_color_input_bwd(fld, g_cin.data_ptr(), ctx.cam.data_ptr(), 1, R, 1, None, 0, None,
+                                                  ctx.d.data_ptr(), ray_grads[1].data_ptr(), _stream()), "tn_color_input_bwd")
+        if ray_grads:
+            starts, ends = _starts_ends(f)
+            _hip.check(lib.tn_frustum_positions_bwd(g_pos.data_ptr(), starts.data_ptr(), ends.data_ptr(), R, S,
+                                                    ray_grads[0].data_ptr(), ray_grads[1].data_ptr(), _stream()),
+                       "tn_frustum_positions_bwd")
+
+    # config.deferred_table_update: both halves on side streams, not joined here (``can_defer`` is False on steps whose third stream
+    # carries the proposal levels' backward: they keep the joined form — that chain and the atomic half would queue behind one another)
+    if hash_encode_bwd(fld.grid, fld.space, f.pos, g_enc, d_table, opts.bucketed, opts.spread, opts.overlap, ray_level_adjoints,
+                       defer=opts.defer and can_defer):
+        _hip.defer(dev, (), [arena.flat, f.enc, g_density, g_rgb_s, g_th_s])
+
+
+def _field_bwd_taped(ctx, opts, arena, grads, ray_grads, sh_grads, g_rgb_s, g_th_s, g_density, g_enc, can_defer: bool) -> None:
+    """the field's backward over the tape: each MLP's layers in one launch (opts.chained) or one launch per layer, then the scatter"""
+    lib = _hip.load()
+    model, f, dev = ctx.model, ctx.field_tape, ctx.o.device
+    h1, bo, cin, c1, c2, rgb_s, t1, t2, _ = ctx.acts
+    R, S = f.weights.shape
+    N = R * S
+    fld = model.field.train_struct()
+
+    def layer(key: str, x: Tensor, x_off: int, act_x: int) -> tuple:
+        """linear_chain_bwd's entry for layer ``key`` reading ``x`` (widths as built: config.hidden_dim / hidden_dim_color /
+        hidden_dim_transient; 64 in the reference's configs)"""
+        w, b = (_grad_view(arena, grads, FIELD_LAYERS[key] + end) for end in (".weight", ".bias"))
+        return (getattr(fld, key), x, x_off, x.shape[1], act_x, w, b)
+
+    ldb = bo.shape[1]
+    g_bo = _f32((N, ldb), dev)  # column 0 written, the geo columns cleared (the += target of both heads) in one pass
+    _hip.check(lib.tn_density_act_bwd(bo.data_ptr(), ldb, f.sel.data_ptr(), fld.average_init_density, opts.exp_min,
+                                      g_density.data_ptr(), N, g_bo.data_ptr(), ldb, ldb, _stream()), "tn_density_act_bwd")
+    if g_th_s is not None:  # thermal branch [REF thermal_field.py:170-179]
+        into_geo = g_bo if model.field.pass_thermal_gradients else None  # REF :171-172 (.detach())
+        th = [layer("thead", t2, 0, ACT_SIGMOID), layer("th1", t1, 0, ACT_RELU), layer("th0", bo, 1, ACT_NONE)]
+        linear_chain_bwd(th, None, ACT_NONE, g_th_s, 1, N, into_geo, 1, ldb, True, opts.chained)
+    if g_rgb_s is not None:  # colour branch [REF :160-168]
+        g_cin = _f32((N, 64), dev)
+        hd = [layer("head2", c2, 0, ACT_RELU), layer("head1", c1, 0, ACT_RELU), layer("head0", cin, 0, ACT_NONE)]
+        linear_chain_bwd(hd, rgb_s, ACT_SIGMOID, g_rgb_s, 3, N, g_cin, 0, 64, False, opts.chained)
+        d_app = _grad_view(arena, grads, "field.embedding_appearance.embedding.weight")
+        _hip.check(lib.tn_color_input_bwd(fld, g_cin.data_ptr(), ctx.cam.data_ptr(), 1, R, S, g_bo.data_ptr() + 4, ldb, d_app.data_ptr(),
+                                          ctx.d.data_ptr() if sh_grads else None, ray_grads[1].data_ptr() if sh_grads else None,
+                                          _stream()), "tn_color_input_bwd")
+    linear_chain_bwd([layer("base1", h1, 0, ACT_RELU), layer("base0", f.enc, 0, ACT_NONE)], None, ACT_NONE, g_bo, ldb, N,
+                     g_enc, 0, f.enc.shape[1], False, opts.chained)
+    hash_encode_bwd(fld.grid, fld.space, f.pos, g_enc, _grad_view(arena, grads, "field.mlp_base.encoder.hash_table"), opts.bucketed, opts.spread,
+                    opts.overlap)
+    if ray_grads:
+        _ray_grads_from_enc(fld.grid, fld.space, f, g_enc, *ray_grads)
 
 
 # --------------------------------------------------------------------------------------------------
 # the step's launch chains as two C-ABI calls (tn_train_step_fwd / tn_train_step_bwd)
 # --------------------------------------------------------------------------------------------------
-def _step_call_applies(model, cfg) -> bool:
-    """config.fused_step_calls (default on) on the default training configuration: tape-free final level, split backward; any
-    other setting keeps the per-call path above (which is also the cross-check: same launches, same streams, same bits)."""
-    return bool(getattr(cfg, "fused_step_calls", True)) and bool(getattr(cfg, "tape_free_training", True)) \
-        and bool(getattr(cfg, "fused_backward_split", True)) and cfg.num_proposal_iterations == 2 and not model.field.staged
-
-
 def _al(n: int) -> int:
     return (n + 63) // 64 * 64  # 256-byte aligned carve-outs
 
@@ -844,12 +883,12 @@ def _slab_layout(sizes):
 
 
 class _StepCall:
-    """RenderTrain's forward / backward on a step whose proposal networks take no gradient, each as ONE library call.  The
-    per-sample tensors of the step live in one slab (they are only ever passed on as addresses), the per-ray outputs in another
-    (the tensors autograd hands back to the caller must not keep ~150 B per sample alive)."""
+    """RenderTrain's forward / backward on a step whose proposal networks take no gradient (_StepOptions.step_call), each as ONE
+    library call.  The per-sample tensors of the step live in one slab (they are only ever passed on as addresses), the per-ray
+    outputs in another (the tensors autograd hands back to the caller must not keep ~150 B per sample alive)."""
 
     @staticmethod
-    def forward(ctx, model, o, d, nears, fars, cam, jitter, params, prop_structs, single):
+    def forward(ctx, model, opts: _StepOptions, o, d, nears, fars, cam, jitter, params, prop_structs, single):
         lib = _hip.load()
         cfg = model.config
         dev = o.device
@@ -862,20 +901,14 @@ class _StepCall:
             raise RuntimeError("config.fused_step_calls needs the reference field geometry (the MFMA chain); set it to False")
         raw, prepared, prepared_bytes = hit
         main, second, third = _step_streams(dev)
-        rays_grad = o.requires_grad or d.requires_grad
-        keep_base = bool(getattr(cfg, "store_base_output", True))
-        keep_jac = rays_grad and bool(getattr(cfg, "store_position_jacobian", True))
         # ---- per-ray slab: everything that leaves as a tensor --------------------------------------------------------------------
         ns = (P0, P1, S)
         shapes = [("rgb", (R, 3)), ("thermal", (R, 1)), ("acc", (R, 1)), ("depth", (R, 1)), ("expected", (R, 1)), ("pd0", (R, 1)),
                   ("pd1", (R, 1))]
         for i, n in enumerate(ns):
             shapes += [("w%d" % i, (R, n)), ("sp%d" % i, (R, n + 1)), ("eu%d" % i, (R, n + 1))]
-        want = getattr(cfg, "overlap_regularisers", "auto")
-        if want == "auto":
-            want = N >= 4096 * 96
         mult_d, mult_i = float(cfg.distortion_loss_mult), float(cfg.interlevel_loss_mult)
-        if want:
+        if opts.regularisers:
             shapes += [("g_dist", (R, S)), ("g_i0", (R, P0)), ("g_i1", (R, P1))]
         off, total = _slab_layout((name, shp[0] * shp[1]) for name, shp in shapes)
         ray_slab = torch.empty((total,), dtype=torch.float32, device=dev)
@@ -884,15 +917,12 @@ class _StepCall:
         rc = render_config(model, True, per_sample_jitter=0 if single else 1)
         need_ws = lib.tn_render_workspace_bytes(rc, R)
         sizes = [("pos", N * 3), ("starts", N), ("ends", N), ("deltas", N), ("ray_bias", R * 64), ("enc", NP * 32), ("sel", N),
-                 ("density", N), ("rgb_s", N * 3), ("th_s", N), ("base_out", N * 16 if keep_base else 0),
-                 ("jac", NP * 96 if keep_jac else 0), ("scratch", 2 * ((R + 3) // 4)), ("ws", (need_ws + 3) // 4)]
+                 ("density", N), ("rgb_s", N * 3), ("th_s", N), ("base_out", N * 16 if opts.keep_base else 0),
+                 ("jac", NP * 96 if opts.keep_jac else 0), ("scratch", 2 * ((R + 3) // 4)), ("ws", (need_ws + 3) // 4)]
         so, stotal = _slab_layout(sizes)
         slab = torch.empty((stotal,), dtype=torch.float32, device=dev)
-        base = slab.data_ptr()
-
-        def ptr(name):
-            return base + 4 * so[name]
-
+        at = {name: slab.data_ptr() + 4 * k for name, k in so.items()}
+        ptr = at.__getitem__
         st = _hip.tn_train_step()
         st.prop0, st.prop1 = C.pointer(prop_structs[0]), C.pointer(prop_structs[1])
         st.field_raw, st.field, st.prepared_bytes = C.pointer(raw), C.pointer(prepared), prepared_bytes
@@ -903,13 +933,13 @@ class _StepCall:
         st.prop_depth[0], st.prop_depth[1] = t["pd0"].data_ptr(), t["pd1"].data_ptr()
         st.positions, st.starts, st.ends, st.deltas, st.ray_bias = ptr("pos"), ptr("starts"), ptr("ends"), ptr("deltas"), ptr("ray_bias")
         st.enc, st.selector, st.density, st.rgb_samples, st.thermal_samples = ptr("enc"), ptr("sel"), ptr("density"), ptr("rgb_s"), ptr("th_s")
-        st.base_out = ptr("base_out") if keep_base else None
-        st.jacobian = ptr("jac") if keep_jac else None
+        st.base_out = ptr("base_out") if opts.keep_base else None
+        st.jacobian = ptr("jac") if opts.keep_jac else None
         st.rgb, st.thermal, st.accumulation = t["rgb"].data_ptr(), t["thermal"].data_ptr(), t["acc"].data_ptr()
         st.depth, st.expected_depth, st.depth_scratch = t["depth"].data_ptr(), t["expected"].data_ptr(), ptr("scratch")
         st.workspace, st.workspace_bytes = ptr("ws"), need_ws
         # the backward's gradient arena: allocated now, cleared by the call on the second stream
-        arena = _GradArena(dict(zip(model.named_parameter_lists()[0], params)), dev, extra=R * (64 + 2 * 64 + S) + 1024, zero=False)
+        arena = _GradArena(dict(zip(model.named_parameter_lists()[0], params)), dev, R, S, zero=False)
         st.zero_buffer, st.zero_bytes = arena.flat.data_ptr(), arena.flat.numel() * 4
         # (the backward joins the second stream before it touches the arena; a training-mode forward that is never differentiated
         # drops the arena with the fill possibly still queued: the allocator must know the second stream used the block)
@@ -917,7 +947,7 @@ class _StepCall:
         slot = (dev, _hip.current_stream())
         _drop_precomputed(slot)
         entry = None
-        if want:
+        if opts.regularisers:
             st.distortion_mult, st.interlevel_mult = mult_d, mult_i
             entry = {"hold": (ray_slab,)}
             w2, c2 = t["w2"], t["sp2"]
@@ -951,10 +981,9 @@ class _StepCall:
         if entry is not None:
             _REG_PRE[slot] = entry
 
-        ctx.set_materialize_grads(False)
         ctx.model, ctx.o, ctx.d, ctx.cam = model, o, d, cam
-        ctx.step_call = (slab, so, ray_slab, off, R, S, keep_base, keep_jac, arena)
-        ctx.updated, ctx.tape_free = False, True
+        ctx.step_call = (slab, so, ray_slab, off, R, S, opts.keep_base, opts.keep_jac, arena)
+        ctx.updated = False
         ctx.tapes = ctx.field_tape = ctx.acts = ctx.acc = None
         ctx.param_names = model.named_parameter_lists()[0]
         ctx.params = dict(zip(ctx.param_names, params))
@@ -974,23 +1003,19 @@ class _StepCall:
         N = R * S
         _drop_precomputed((dev, _hip.current_stream()))
         fld = model.field.train_struct()
-        ray_grads = None
-        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
-            ray_grads = (arena.zeros(tuple(ctx.o.shape)), arena.zeros(tuple(ctx.d.shape)))
+        ray_grads = _ray_grad_buffers(ctx, arena)
+        opts = _step_options(model, cfg, R, S, ray_grads is not None)
         sh_grads = ray_grads is not None and bool(cfg.sh_direction_gradient)
         grads: Dict[str, Tensor] = {}
-        base, rbase = slab.data_ptr(), ray_slab.data_ptr()
-
-        def ptr(name):
-            return base + 4 * so[name]
-
+        at = {name: slab.data_ptr() + 4 * k for name, k in so.items()}
+        ptr = at.__getitem__
         a = _hip.tn_train_step_bwd_args()
         a.field, a.num_rays, a.n = C.pointer(fld), R, S
         a.positions, a.starts, a.ends, a.deltas, a.ray_bias = ptr("pos"), ptr("starts"), ptr("ends"), ptr("deltas"), ptr("ray_bias")
         a.enc, a.selector, a.density, a.rgb_samples, a.thermal_samples = ptr("enc"), ptr("sel"), ptr("density"), ptr("rgb_s"), ptr("th_s")
         a.base_out = ptr("base_out") if keep_base else None
         a.jacobian = ptr("jac") if keep_jac else None
-        a.accumulation = rbase + 4 * off["acc"]
+        a.accumulation = ray_slab.data_ptr() + 4 * off["acc"]
         a.directions, a.camera_indices = ctx.d.data_ptr(), ctx.cam.data_ptr()
         hold = []  # contiguous copies of the incoming gradients live until the call has been queued (same stream: no race)
         for name, g in (("d_rgb", g_rgb), ("d_thermal", g_th), ("d_accumulation", g_acc), ("d_weights", g_w2)):
@@ -1000,17 +1025,11 @@ class _StepCall:
                 setattr(a, name, g.data_ptr())
         a.use_gradient_scaling = 1 if cfg.use_gradient_scaling else 0
         a.pass_thermal_gradients = 1 if model.field.pass_thermal_gradients else 0
-        a.split_form = 2 if getattr(cfg, "backward_bf16_pieces", True) else 1
+        a.split_form = opts.split_form
         a.sh_direction_gradient = 1 if sh_grads else 0
-        a.trunc_exp_min = float(getattr(cfg, "trunc_exp_clamp_min", -15.0))
+        a.trunc_exp_min = opts.exp_min
         # scratch of the backward: one slab (addresses only)
-        first = -1
-        bucketed = getattr(cfg, "bucketed_table_scatter", True)
-        if bucketed is True:
-            first = lib.tn_hash_encode_bwd_sorted_first_level(fld.grid, N)
-        elif bucketed is not False and bucketed is not None:
-            first = int(bucketed)  # (tests, tools/train_bench.py --first-sorted-level: bucketed from that level on)
-        need_sorted = lib.tn_hash_encode_bwd_sorted_workspace_bytes(fld.grid, N, first) if first >= 0 else 0
+        first, need_sorted = _sorted_plan(lib, fld.grid, N, opts.bucketed)
         sizes = [("g_rgb_s", N * 3 if g_rgb is not None else 0), ("g_th_s", N if g_th is not None else 0), ("g_density", N), ("g_enc", N * 32),
                  ("g_pos", N * 3 if ray_grads else 0), ("g_cin", R * 64 if (sh_grads and g_rgb is not None) else 0),
                  ("sorted", (need_sorted + 3) // 4)]
@@ -1026,29 +1045,13 @@ class _StepCall:
         a.d_density, a.d_enc = bb + 4 * bo["g_density"], bb + 4 * bo["g_enc"]
         a.d_positions = bb + 4 * bo["g_pos"] if ray_grads else None
         a.d_ray_inputs = bb + 4 * bo["g_cin"] if (sh_grads and g_rgb is not None) else None
-        gr = _hip.tn_field_grads()
-        names = {"base0": "field.mlp_base.mlp.layers.0", "base1": "field.mlp_base.mlp.layers.1",
-                 "head0": "field.mlp_head.layers.0", "head1": "field.mlp_head.layers.1", "head2": "field.mlp_head.layers.2",
-                 "th0": "field.mlp_thermal.layers.0", "th1": "field.mlp_thermal.layers.1", "thead": "field.field_head_thermal.net"}
-
-        def zeros(name: str) -> Tensor:
-            grads[name] = arena.get(name)
-            return grads[name]
-
-        for key, name in names.items():
-            if key.startswith("head") and g_rgb is None:
-                continue
-            if key.startswith("th") and g_th is None:
-                continue
-            setattr(gr, key + "_w", zeros(name + ".weight").data_ptr())
-            if key != "head0":
-                setattr(gr, key + "_b", zeros(name + ".bias").data_ptr())
+        gr = _bind_field_grads(arena, grads, g_rgb is not None, g_th is not None)
         a.grads = C.pointer(gr)
         if g_rgb is not None:
             a.d_ray_sum = arena.zeros((R, 64)).data_ptr()
-            a.d_head0_bias = zeros("field.mlp_head.layers.0.bias").data_ptr()
-            a.d_appearance = zeros("field.embedding_appearance.embedding.weight").data_ptr()
-        a.d_table = zeros("field.mlp_base.encoder.hash_table").data_ptr()
+            a.d_head0_bias = _grad_view(arena, grads, "field.mlp_head.layers.0.bias").data_ptr()
+            a.d_appearance = _grad_view(arena, grads, "field.embedding_appearance.embedding.weight").data_ptr()
+        a.d_table = _grad_view(arena, grads, "field.mlp_base.encoder.hash_table").data_ptr()
         if ray_grads:
             a.d_origins, a.d_directions = ray_grads[0].data_ptr(), ray_grads[1].data_ptr()
         ws = _fused_bwd_workspace(dev, R, S)
@@ -1057,27 +1060,23 @@ class _StepCall:
         if need_sorted:
             a.sorted_workspace, a.sorted_workspace_bytes = bb + 4 * bo["sorted"], need_sorted
         main, second, third = _step_streams(dev)
-        overlap = bool(getattr(cfg, "overlap_table_scatter", True))
-        defer = bool(getattr(cfg, "deferred_table_update", False)) and overlap and first > 0
-        a.spread = 1 if getattr(cfg, "spread_coarse_scatter", True) else 0
-        if a.spread:
-            need = lib.tn_hash_encode_bwd_spread_workspace_bytes(fld.grid)
+        defer = opts.defer and first > 0  # (a scatter without a bucketed part is joined)
+        a.spread = 1 if opts.spread else 0
+        if a.spread:  # the atomic half's private copies: on the stream that half runs on
+            sws, need = _spread_workspace(lib, fld.grid, dev, third.cuda_stream if defer else main.cuda_stream)
             if need:
-                key = (dev, third.cuda_stream if defer else main.cuda_stream, need)
-                sws = _SPREAD_WS.get(key)
-                if sws is None:
-                    sws = _SPREAD_WS[key] = torch.empty(need, dtype=torch.uint8, device=dev)
                 a.spread_workspace, a.spread_workspace_bytes = sws.data_ptr(), need
-        a.overlap, a.defer = (1 if overlap else 0), (1 if defer else 0)
+        a.overlap, a.defer = (1 if opts.overlap else 0), (1 if defer else 0)
         a.wait_second_first = 1  # the arena was cleared on the second stream (tn_train_step_fwd)
         a.stream, a.second, a.third = main.cuda_stream, second.cuda_stream, third.cuda_stream
         _hip.check(lib.tn_train_step_bwd(C.byref(a)), "tn_train_step_bwd")
         if defer:  # both halves of the scatter are still out: whoever reads the table (or its gradient) joins (_hip.join_pending)
             _hip.defer(dev, [second, third], [bslab, slab, ray_slab, arena.flat])
-        g_o, g_d = ray_grads if ray_grads else (None, None)
-        result = (None, g_o, g_d) + (None,) * 5 + tuple(grads.get(n) for n in ctx.param_names)
+        result = _grad_result(ctx, ray_grads, grads)
         ctx.step_call = None
         return result
+
+
 
 
 # --------------------------------------------------------------------------------------------------
@@ -1146,17 +1145,12 @@ def _drop_precomputed(slot) -> None:
             main.wait_stream(entry[which][2])
 
 
-def _precompute_regularisers(model, w_levels: Sequence[Tensor], c_levels: Sequence[Tensor]) -> None:
+def _precompute_regularisers(model, opts: _StepOptions, w_levels: Sequence[Tensor], c_levels: Sequence[Tensor]) -> None:
     cfg = model.config
     dev = w_levels[-1].device
     slot = (dev, _hip.current_stream())
     _drop_precomputed(slot)  # an earlier forward's results nobody collected (an exception, a forward without losses)
-    want = getattr(cfg, "overlap_regularisers", "auto")
-    if want == "auto":
-        # the side launches cost the host four stream joins (~40 us): they pay once the step's device time is well above its
-        # host time — S=192: 2.64 against 2.68 ms per step; S=48 (device 1.34 ms, host ~1 ms): 1.34-1.46 against 1.34-1.35
-        want = w_levels[-1].numel() >= 4096 * 96
-    if not want or len(w_levels) < 2:
+    if not opts.regularisers or len(w_levels) < 2:
         return
     _, second, third = _step_streams(dev)
     w2, c2 = w_levels[-1], c_levels[-1]

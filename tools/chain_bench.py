@@ -50,8 +50,8 @@ def main():
     us = e0.elapsed_time(e1) * 1e3 / a.reps
     flops = 2 * 2 * n * (3 * 64 + 64 * 64 + 64 * 64)
     if "timing" in os.environ.get("THERMONERF_HIP_LIB", ""):
-        from thermo_nerf_amd.training import _CHAIN_WS
-        ws = _CHAIN_WS[dev]
+        from thermo_nerf_amd.training import _WORKSPACES
+        ws = _WORKSPACES[("chain", dy.device, _hip.current_stream())]
         cnt = ws[-64:].view(torch.int64).cpu().tolist()
         tiles = (n + 63) // 64 * (a.reps + 3)
         names = ["epilogue of the layer below / g0 stage (+barrier)", "stage x_j + barrier", "dW MFMAs", "bias sums", "dx MFMAs",
