@@ -581,6 +581,59 @@ int tn_voxel_downsample(const float *positions, const uint8_t *colors, const flo
                         uint8_t *colors_out, float *temperature_out, uint8_t *thermal_colors_out, int64_t *source_out,
                         int32_t *voxel_count, int64_t capacity, int64_t *count, void *workspace, size_t workspace_bytes, void *stream);
 
+/* Vertex-clustering simplification of an indexed triangle list: the vertices that fall in one cell of a grid become one vertex, the
+ * triangles are re-indexed, and those that collapse or repeat go.  positions [V, 3] floats, colors / thermal_colors [V, 3] bytes,
+ * temperature [V] floats, triangles [T, 3] int32, V = num_vertices, T = num_triangles.  Every output is defined to the bit.
+ *   parameters   tn_voxel_params as in tn_voxel_downsample: origin, voxel_size (the cell edge), dims; the same limits and the same
+ *                TN_ERR_UNSUPPORTED.
+ *   member, cell, key   exactly tn_voxel_downsample's: u_a = ((double)p_a - (double)origin_a) * (1.0 / (double)voxel_size); a
+ *                vertex is a MEMBER iff its three coordinates are finite and 0 <= u_a < dims_a on every axis; c_a = (int64)u_a;
+ *                key = (c_z * dims_y + c_y) * dims_x + c_x.  A CLUSTER is the set of members with one key.
+ *   triangle     VALID iff its three indices are in [0, V) and all three vertices are members.  Its cluster triple is (A, B, C), the
+ *                clusters of its corners in corner order; it is DEGENERATE iff two of them are equal.  Its CANONICAL triple is the
+ *                cyclic rotation of (A, B, C) that puts the smallest cluster first; orientation is kept: (A, B, C) and (A, C, B)
+ *                are different triples.  Among the valid, non-degenerate triangles with one canonical triple the one with the
+ *                lowest input index is KEPT, the others are DUPLICATES.
+ *   vertices     a cluster is USED iff a kept triangle names it.  One output vertex per used cluster, in ascending key; an unused
+ *                cluster (vertices in no triangle, an island that collapsed into one cell) gives nothing.
+ *   positions_out, temperature_out   per component the fp64 sum from 0 over ALL members of the cluster in ascending vertex index
+ *                (unreferenced members count too), divided by (double)n, rounded once to fp32.
+ *   colors_out, thermal_colors_out (uint8)   per channel the exact integer sum S, then (2 S + n) / (2 n) in integer division
+ *                (round half up).  thermal_colors_out may be NULL, and must be if thermal_colors is.
+ *   cluster_count   int32 n per output vertex.
+ *   triangles_out (int32 [capacity_triangles, 3])   the kept triangles in ascending input index, every corner rewritten to the
+ *                output vertex of its cluster; the corner order is the input's, not the canonical rotation.
+ *   triangle_source (int32 [capacity_triangles], may be NULL)   the input index of every output triangle.
+ *   vertex_map (int32 [V], may be NULL)   per input vertex the output vertex of its cluster; -1 for a non-member and for a member of
+ *                an unused cluster.
+ *   counts (device int64 [4], OVERWRITTEN)   [0] output vertices, [1] output triangles, [2] triangles dropped as invalid or
+ *                degenerate, [3] triangles dropped as duplicates; [1] + [2] + [3] = T.  The FULL numbers: nothing is written at
+ *                or beyond a capacity (both 0 with NULL outputs: the sizing call).
+ * How: the vertex keys are sorted with the vertex indices by tn_sort_pairs and the heads of the runs compacted (count, one-block
+ * scan, emit), which ranks the clusters; one thread per triangle forms the canonical triple of ranks; with b = bit_length(V) the
+ * triples are sorted with the triangle indices as ONE key of 3 b + 1 bits if that fits 64 (V < 2^21), otherwise by TWO stable sorts
+ * (the third rank, then the first two), so that equal triples are adjacent in ascending triangle index; the head of a run is kept
+ * and flags its three clusters; two more compactions (triangles in input order, clusters in key order); one thread per used cluster
+ * walks its run for the means.  workspace: tn_mesh_simplify_workspace_bytes(V, T) device bytes, 8-byte aligned; 0 for counts out of
+ * range.  Launches on `stream` only: no allocation, no host synchronisation, no float atomics, no block waits for another.  The
+ * integer atomics (the sort's LDS histogram, one add per block to counts[2]) and the same-value flag stores leave nothing in any
+ * output that depends on the order of arrival.  The walk is sequential per cluster (the sums are ordered by definition): a cluster
+ * of 10^5 members is 10^5 steps of one thread.
+ * TN_ERR_NULL: params or counts is NULL; positions, colors, temperature or the workspace with V > 0; triangles with T > 0;
+ * positions_out, colors_out, temperature_out or cluster_count with capacity_vertices > 0; triangles_out with capacity_triangles > 0;
+ * thermal_colors_out without thermal_colors; TN_ERR_SHAPE: V < 0 or > 2^31 - 1, T < 0 or 3T > 2^31 - 1, a negative capacity, a
+ * float / int32 pointer not 4-byte aligned, counts / workspace not 8-byte aligned; TN_ERR_WORKSPACE: workspace_bytes too small.
+ * All are returned before any launch.  V == 0: TN_OK, counts is zeroed by a memset, nothing is launched (the one case in which the
+ * triangles, all of them invalid, are not counted in [2]).  T == 0 with V > 0: counts is zeroed and vertex_map filled with -1, by
+ * memsets. */
+size_t tn_mesh_simplify_workspace_bytes(int64_t num_vertices, int64_t num_triangles);
+int tn_mesh_simplify(const float *positions, const uint8_t *colors, const float *temperature, const uint8_t *thermal_colors,
+                     const int32_t *triangles, int64_t num_vertices, int64_t num_triangles, const tn_voxel_params *params,
+                     float *positions_out, uint8_t *colors_out, float *temperature_out, uint8_t *thermal_colors_out,
+                     int32_t *cluster_count, int64_t capacity_vertices, int32_t *triangles_out, int32_t *triangle_source,
+                     int64_t capacity_triangles, int32_t *vertex_map, int64_t *counts, void *workspace, size_t workspace_bytes,
+                     void *stream);
+
 /* ------------------------------------------------------------------------------------------------------
  * Fused forward: Model.forward (collider) + ThermalNerfModel.get_outputs
  * [REF thermal_nerf_model.py:210-275]

@@ -241,6 +241,9 @@ SIGNATURES = {
     "tn_sort_pairs": (C.c_int, [_vp, _vp, _i64, C.c_int, _vp, _vp, _vp, _sz, _vp]),
     "tn_voxel_downsample_workspace_bytes": (_sz, [_i64]),
     "tn_voxel_downsample": (C.c_int, [_vp] * 5 + [_i64, C.POINTER(tn_voxel_params)] + [_vp] * 6 + [_i64, _vp, _vp, _sz, _vp]),
+    "tn_mesh_simplify_workspace_bytes": (_sz, [_i64, _i64]),
+    "tn_mesh_simplify": (C.c_int, [_vp] * 5 + [_i64, _i64, C.POINTER(tn_voxel_params)] + [_vp] * 5 + [_i64, _vp, _vp, _i64, _vp, _vp, _vp,
+                                   _sz, _vp]),
     "tn_mesh_tile": (_i32, []),
     "tn_mesh_scan_width": (_i32, []),
     "tn_mesh_workspace_bytes": (_sz, [_i32, _i32, _i32]),

@@ -12,6 +12,7 @@
 // tens to hundreds).
 #include "tn_device.h"
 #include "tn_scan.h"
+#include "tn_voxel_grid.h"
 
 using namespace tn;
 
@@ -19,40 +20,18 @@ namespace {
 
 constexpr int kTile = 256;  // points / sorted positions / voxels per block of every kernel but the scan
 
-struct VoxelGrid {
-    double origin[3];
-    double inv;       // 1.0 / (double)voxel_size
-    double limit[3];  // (double)dims
-    unsigned long long dims_x, dims_y, total;
-};
-
 __global__ void __launch_bounds__(kTile)
 keys_kernel(const float *__restrict__ positions, long long n, VoxelGrid g, unsigned long long *__restrict__ keys) {
     const long long i = (long long)blockIdx.x * kTile + threadIdx.x;
     if (i >= n) return;
-    unsigned long long c[3];
-    bool member = true;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        const float p = positions[3 * i + a];
-        const double u = __dmul_rn(__dsub_rn((double)p, g.origin[a]), g.inv);
-        member = member && isfinite(p) && u >= 0.0 && u < g.limit[a];  // (a NaN fails)
-        c[a] = member ? (unsigned long long)(long long)u : 0ull;
-    }
-    keys[i] = member ? (c[2] * g.dims_y + c[1]) * g.dims_x + c[0] : g.total;
-}
-
-__device__ __forceinline__ bool is_head(const unsigned long long *__restrict__ keys, long long j, long long n, unsigned long long total) {
-    if (j >= n) return false;
-    const unsigned long long k = keys[j];
-    return k < total && (j == 0 || k != keys[j - 1]);
+    keys[i] = voxel_key(positions, i, g);
 }
 
 __global__ void __launch_bounds__(kTile)
 count_heads_kernel(const unsigned long long *__restrict__ keys, long long n, unsigned long long total, long long *__restrict__ tiles) {
     const long long j = (long long)blockIdx.x * kTile + threadIdx.x;
     uint32_t heads;
-    block_rank<kTile>(is_head(keys, j, n, total), heads);
+    block_rank<kTile>(voxel_head(keys, j, n, total), heads);
     if (threadIdx.x == 0) tiles[blockIdx.x] = (long long)heads;
 }
 
@@ -65,7 +44,7 @@ __global__ void __launch_bounds__(kTile)
 emit_heads_kernel(const unsigned long long *__restrict__ keys, long long n, unsigned long long total, const long long *__restrict__ tiles,
                   int *__restrict__ heads) {
     const long long j = (long long)blockIdx.x * kTile + threadIdx.x;
-    const bool head = is_head(keys, j, n, total);
+    const bool head = voxel_head(keys, j, n, total);
     uint32_t unused;
     const uint32_t rank = block_rank<kTile>(head, unused);
     if (!head) return;
@@ -73,60 +52,15 @@ emit_heads_kernel(const unsigned long long *__restrict__ keys, long long n, unsi
     if (v < n) heads[v] = (int)j;
 }
 
-struct Cloud {
-    const float *positions, *temperature;
-    const uint8_t *colors, *thermal_colors;  // thermal_colors may be NULL
-    const long long *source;                 // may be NULL
-};
-
-struct CloudOut {
-    float *positions, *temperature;
-    uint8_t *colors, *thermal_colors;
-    long long *source;
-    int *voxel_count;
-};
-
-__device__ __forceinline__ uint8_t rounded_mean(unsigned long long sum, unsigned long long members) {
-    return (uint8_t)((2ull * sum + members) / (2ull * members));  // round half up; at most 255
-}
-
 __global__ void __launch_bounds__(kTile)
 average_kernel(const unsigned long long *__restrict__ keys, const int *__restrict__ order, long long n, const int *__restrict__ heads,
-               const long long *__restrict__ count, long long capacity, Cloud in, CloudOut out) {
+               const long long *__restrict__ count, long long capacity, VoxelInputs in, VoxelOutputs out,
+               const long long *__restrict__ source, long long *__restrict__ source_out) {  // both may be NULL
     const long long v = (long long)blockIdx.x * kTile + threadIdx.x;
     if (v >= capacity || v >= count[0]) return;
     const long long start = heads[v];
-    const unsigned long long key = keys[start];
-    double sum[4] = {0.0, 0.0, 0.0, 0.0};
-    unsigned long long rgb[3] = {0, 0, 0}, thermal_rgb[3] = {0, 0, 0};
-    long long j = start;
-    for (; j < n && keys[j] == key; ++j) {
-        const long long i = order[j];
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            sum[a] = __dadd_rn(sum[a], (double)in.positions[3 * i + a]);
-            rgb[a] += in.colors[3 * i + a];
-        }
-        sum[3] = __dadd_rn(sum[3], (double)in.temperature[i]);
-        if (in.thermal_colors) {
-#pragma unroll
-            for (int a = 0; a < 3; ++a) thermal_rgb[a] += in.thermal_colors[3 * i + a];
-        }
-    }
-    const unsigned long long members = (unsigned long long)(j - start);  // >= 1: a head is a member
-    const double m = (double)members;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        out.positions[3 * v + a] = (float)__ddiv_rn(sum[a], m);
-        out.colors[3 * v + a] = rounded_mean(rgb[a], members);
-    }
-    out.temperature[v] = (float)__ddiv_rn(sum[3], m);
-    if (out.thermal_colors) {
-#pragma unroll
-        for (int a = 0; a < 3; ++a) out.thermal_colors[3 * v + a] = rounded_mean(thermal_rgb[a], members);
-    }
-    if (out.source) out.source[v] = in.source[order[start]];
-    out.voxel_count[v] = (int)members;
+    voxel_average(keys, order, n, start, in, out, v);
+    if (source_out) source_out[v] = source[order[start]];
 }
 
 inline bool bad_count(int64_t n) { return n < 0 || n > 0x7fffffffLL; }
@@ -136,12 +70,6 @@ inline long long tiles_of(long long n) { return ceil_div(n, kTile); }
 inline size_t keys_bytes(long long n) { return (size_t)n * sizeof(unsigned long long); }
 
 inline size_t ints_bytes(long long n) { return ((size_t)n * sizeof(int) + 7) / 8 * 8; }
-
-inline int bit_length(unsigned long long x) {
-    int bits = 0;
-    for (; x; x >>= 1) ++bits;
-    return bits;
-}
 
 }  // namespace
 
@@ -160,9 +88,7 @@ int tn_voxel_downsample(const float *positions, const uint8_t *colors, const flo
                         int32_t *voxel_count, int64_t capacity, int64_t *count, void *workspace, size_t workspace_bytes, void *stream) {
     if (!params || !count) return TN_ERR_NULL;
     if (bad_count(num_points) || capacity < 0) return TN_ERR_SHAPE;
-    if (!(params->voxel_size > 0.0f) || !(params->voxel_size <= 3.402823466e+38f)) return TN_ERR_UNSUPPORTED;  // (a NaN fails the first)
-    for (int a = 0; a < 3; ++a)
-        if (params->dims[a] < 1 || params->dims[a] > (1 << 21)) return TN_ERR_UNSUPPORTED;
+    if (voxel_params_unsupported(params)) return TN_ERR_UNSUPPORTED;
     if (num_points > 0 && (!positions || !colors || !temperature || !workspace)) return TN_ERR_NULL;
     if (capacity > 0 && (!positions_out || !colors_out || !temperature_out || !voxel_count)) return TN_ERR_NULL;
     if (num_points > 0 && ((thermal_colors_out && !thermal_colors) || (source_out && !source))) return TN_ERR_NULL;
@@ -174,15 +100,7 @@ int tn_voxel_downsample(const float *positions, const uint8_t *colors, const flo
     hipStream_t s = (hipStream_t)stream;
     if (num_points == 0) return hipMemsetAsync(count, 0, sizeof(int64_t), s) == hipSuccess ? TN_OK : TN_ERR_LAUNCH;
     const long long n = (long long)num_points;
-    VoxelGrid g;
-    for (int a = 0; a < 3; ++a) {
-        g.origin[a] = (double)params->origin[a];
-        g.limit[a] = (double)params->dims[a];
-    }
-    g.inv = 1.0 / (double)params->voxel_size;
-    g.dims_x = (unsigned long long)params->dims[0];
-    g.dims_y = (unsigned long long)params->dims[1];
-    g.total = g.dims_x * g.dims_y * (unsigned long long)params->dims[2];  // <= 2^63
+    const VoxelGrid g = voxel_grid_of(params);
     char *ws = reinterpret_cast<char *>(workspace);
     unsigned long long *keys = reinterpret_cast<unsigned long long *>(ws);
     unsigned long long *sorted_keys = reinterpret_cast<unsigned long long *>(ws + keys_bytes(n));
@@ -206,11 +124,11 @@ int tn_voxel_downsample(const float *positions, const uint8_t *colors, const flo
     TN_LAUNCH_CHECK();
     const long long walkers = capacity < n ? (long long)capacity : n;  // there are at most n voxels
     if (walkers > 0) {
-        const Cloud in = {positions, temperature, colors, thermal_colors, reinterpret_cast<const long long *>(source)};
-        const CloudOut out = {positions_out, temperature_out, colors_out, thermal_colors_out, reinterpret_cast<long long *>(source_out),
-                              voxel_count};
+        const VoxelInputs in = {positions, temperature, colors, thermal_colors};
+        const VoxelOutputs out = {positions_out, temperature_out, colors_out, thermal_colors_out, voxel_count};
         hipLaunchKernelGGL(average_kernel, dim3((unsigned)tiles_of(walkers)), dim3(kTile), 0, s, sorted_keys, order, n, heads, cnt,
-                           (long long)capacity, in, out);
+                           (long long)capacity, in, out, reinterpret_cast<const long long *>(source),
+                           reinterpret_cast<long long *>(source_out));
         TN_LAUNCH_CHECK();
     }
     return TN_OK;

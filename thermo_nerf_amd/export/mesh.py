@@ -241,6 +241,7 @@ class MeshExporter(PoseExporter):
         self.params = mesh_params(box[0], box[1], self.dims, truncation, min_accumulation, max_temperature, min_temperature, to_world)
         self.last_poses = 0  # poses fused by the last export
         self.last_components = None  # the ComponentsInfo of the last export, None when it removed no components
+        self.last_simplify = None  # the SimplifyInfo of the last export, None when it did not simplify
 
     @torch.no_grad()
     def fuse(self, cameras, camera_indices: Optional[Sequence[int]] = None, apply_camera_optimizer: bool = True) -> Tensor:
@@ -282,7 +283,8 @@ class MeshExporter(PoseExporter):
 
     def export(self, cameras, camera_indices: Optional[Sequence[int]] = None, apply_camera_optimizer: bool = True,
                min_component_triangles: int = 0, largest_component: bool = False, smooth_iterations: int = 0,
-               smooth_lambda: float = 0.5, smooth_mu: float = -0.53, normals: bool = False) -> ThermalMesh:
+               smooth_lambda: float = 0.5, smooth_mu: float = -0.53, normals: bool = False,
+               simplify_cell_size: float = 0.0) -> ThermalMesh:
         """Fuse ``cameras`` (all, or ``camera_indices``) in that order and return the surface.  ``apply_camera_optimizer``: adjust
         camera k's rays with row k of the model's pose table — right for the TRAINING cameras (pass False for other views).
         Cameras are rendered as PINHOLE views: ``distortion_params`` is ignored, because the export renders the model — it does
@@ -290,6 +292,10 @@ class MeshExporter(PoseExporter):
         ``min_component_triangles`` > 0 drops the connected components (the islands floaters turn into) of fewer triangles,
         ``largest_component`` all but the largest (``remove_small_components``; ``last_components`` then tells what went).  With
         both off the mesh is the extraction's, untouched.
+        ``simplify_cell_size`` > 0 then merges the vertices that share a grid cell of that edge — in the units of the positions as
+        written, world units with ``to_world`` — into one averaged vertex and drops the triangles that collapse or repeat
+        (``simplify_mesh``; ``last_simplify`` then tells what went).  It runs after the components are removed and before the
+        smoothing, which relaxes the clustered surface; the normals are those of the final surface.
         ``smooth_iterations`` > 0 then relaxes the positions by that many Taubin iterations with the factors ``smooth_lambda`` /
         ``smooth_mu`` (``smooth_mesh``; colours and temperature do not move), and ``normals`` adds the area-weighted vertex normals
         of the FINAL positions and triangles.  With both off none of that code is called."""
@@ -297,12 +303,19 @@ class MeshExporter(PoseExporter):
             raise ValueError("min_component_triangles must not be negative")
         if int(smooth_iterations) < 0:
             raise ValueError("smooth_iterations must not be negative")
+        cell_size = float(simplify_cell_size)
+        if not (cell_size >= 0.0 and math.isfinite(cell_size)):
+            raise ValueError("simplify_cell_size must be finite and not negative")
         mesh = self.extract(self.fuse(cameras, camera_indices, apply_camera_optimizer))
-        self.last_components = None
+        self.last_components = self.last_simplify = None
         if int(min_component_triangles) > 0 or largest_component:
             from .components import remove_small_components
 
             mesh, self.last_components = remove_small_components(mesh, int(min_component_triangles), bool(largest_component))
+        if cell_size > 0.0:
+            from .simplify import simplify_mesh
+
+            mesh, self.last_simplify = simplify_mesh(mesh, cell_size)
         if int(smooth_iterations) > 0 or normals:
             from .smooth import smooth_mesh
 

@@ -24,6 +24,14 @@ Surface nets place a vertex at the mean of its cell's edge crossings, so the fac
 
     python tools/export_mesh.py RUN_DIR DATASET --output mesh.ply --resolution 256 --smooth-iterations 10 --normals
 
+At ``--resolution 256`` a room comes out at a density set by the voxel grid, not by what a viewer needs.  ``--simplify-cell-size S``
+merges the vertices that share a cell of a grid of edge S — in the units of the written positions: world units, as ``--voxel-size``
+of tools/export_pointcloud.py, or scene units with ``--scene-frame`` — into one vertex with their mean position, colour and
+temperature, and drops the triangles that collapse or repeat (vertex clustering).  It runs after the components are removed and
+before the smoothing; 0 (the default) is off:
+
+    python tools/export_mesh.py RUN_DIR DATASET --output mesh.ply --resolution 256 --simplify-cell-size 0.05 --smooth-iterations 5
+
 Positions are written in the dataset's original world frame; ``--scene-frame`` keeps the normalised frame the model was trained in.
 """
 from __future__ import annotations
@@ -58,6 +66,8 @@ def parse(argv=None) -> argparse.Namespace:
     ap.add_argument("--min-component-triangles", type=int, default=0, metavar="N",
                     help="drop connected components of fewer than N triangles (0: off)")
     ap.add_argument("--largest-component", action="store_true", help="keep only the connected component with the most triangles")
+    ap.add_argument("--simplify-cell-size", type=float, default=0.0, metavar="S",
+                    help="merge the vertices that share a grid cell of edge S, in the units of the written positions (0: off)")
     ap.add_argument("--smooth-iterations", type=int, default=0, metavar="N", help="Taubin smoothing iterations (0: off)")
     ap.add_argument("--smooth-lambda", type=float, default=0.5, help="the factor of an iteration's first pass (> 0)")
     ap.add_argument("--smooth-mu", type=float, default=-0.53, help="the factor of an iteration's second pass (< -lambda)")
@@ -74,6 +84,8 @@ def parse(argv=None) -> argparse.Namespace:
         ap.error("--min-component-triangles must not be negative")
     if args.smooth_iterations < 0:
         ap.error("--smooth-iterations must not be negative")
+    if not (args.simplify_cell_size >= 0.0 and math.isfinite(args.simplify_cell_size)):
+        ap.error("--simplify-cell-size must be finite and not negative")
     if not (args.smooth_lambda > 0.0 and args.smooth_mu < -args.smooth_lambda and math.isfinite(args.smooth_lambda)
             and math.isfinite(args.smooth_mu)):
         ap.error("--smooth-lambda must be positive and --smooth-mu below its negative, both finite")
@@ -102,7 +114,8 @@ def main(argv=None) -> int:
     exporter, cameras, adjust = build_exporter(args)
     mesh = exporter.export(cameras, apply_camera_optimizer=adjust, min_component_triangles=args.min_component_triangles,
                            largest_component=args.largest_component, smooth_iterations=args.smooth_iterations,
-                           smooth_lambda=args.smooth_lambda, smooth_mu=args.smooth_mu, normals=args.normals)
+                           smooth_lambda=args.smooth_lambda, smooth_mu=args.smooth_mu, normals=args.normals,
+                           simplify_cell_size=args.simplify_cell_size)
     write_mesh_ply(args.output, mesh, colors=args.colors)
     nx, ny, nz = exporter.dims
     print(f"poses fused {exporter.last_poses} into {nx} x {ny} x {nz}, vertices {len(mesh)}, triangles {int(mesh.triangles.shape[0])}, "
@@ -111,6 +124,11 @@ def main(argv=None) -> int:
     if info is not None:
         print(f"components found {info.components}, largest {info.largest_triangles} triangles, removed vertices {info.vertices_removed}, "
               f"triangles {info.triangles_removed}")
+    info = exporter.last_simplify
+    if info is not None:
+        print(f"simplified with cell size {args.simplify_cell_size:g}: vertices {info.vertices_before} -> {info.vertices_after}, triangles "
+              f"{info.triangles_before} -> {info.triangles_after} (degenerate {info.degenerate_triangles}, duplicate "
+              f"{info.duplicate_triangles})")
     if len(mesh):
         print(f"temperature min {float(mesh.temperature.min()):.3f} C, max {float(mesh.temperature.max()):.3f} C")
     else:
