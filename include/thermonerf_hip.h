@@ -634,6 +634,74 @@ int tn_mesh_simplify(const float *positions, const uint8_t *colors, const float 
                      int64_t capacity_triangles, int32_t *vertex_map, int64_t *counts, void *workspace, size_t workspace_bytes,
                      void *stream);
 
+/* Thermal regions of an indexed triangle list: the faces whose temperature lies in a window, joined through shared vertices, and per
+ * region its area, area-weighted mean temperature and centroid, extremes, bounds and hottest / coldest vertex.  positions [V, 3]
+ * floats, temperature [V] floats, triangles [T, 3] int32, V = num_vertices, T = num_triangles.  Every output is defined to the bit.
+ * add / sub / mul / div / sqrt below are single correctly rounded fp64 operations, nothing is contracted; (double) of a float is
+ * exact, (float) of a double rounds to nearest even.
+ *   face t, indices i0 i1 i2, positions p0 p1 p2, temperatures t0 t1 t2:
+ *     VALID     all three indices in [0, V).
+ *     USABLE    valid, the three indices distinct, all nine coordinates finite, all three temperatures finite.
+ *     tf        (float)div(add(add((double)t0, (double)t1), (double)t2), 3.0)
+ *     area      e1 = sub(p1, p0), e2 = sub(p2, p0) per component; c = (sub(mul(e1y, e2z), mul(e1z, e2y)), sub(mul(e1z, e2x),
+ *               mul(e1x, e2z)), sub(mul(e1x, e2y), mul(e1y, e2x))) — the face vector of tn_mesh_vertex_normals in fp64;
+ *               n2 = add(add(mul(cx, cx), mul(cy, cy)), mul(cz, cz)); area = mul(0.5, sqrt(n2)).
+ *     centroid  per axis div(add(add(p0, p1), p2), 3.0)
+ *     SELECTED  usable and min_temperature <= tf <= max_temperature, compared in fp32.  Either bound may be infinite; min > max
+ *               selects nothing.
+ *   face_area (double [T], may be NULL): the area of a usable face, +0.0 of every other.
+ *   regions     two selected faces that share a vertex are connected (the connectivity of tn_mesh_components, over the selected
+ *               faces only).  A region's LABEL is the smallest vertex index among its faces' vertices; regions are numbered
+ *               r = 0 .. R-1 in ascending label; a region's faces are taken in ascending face index.
+ *   face_region (int32 [T], always fully written): r of a selected face, -1 of every other.
+ *   SUM2(list)  the ordered sum: the list is cut into consecutive blocks of 256 entries from its start (the last may be short); each
+ *               block is accumulated from +0.0 in list order, s = add(s, x); the block sums are then accumulated from +0.0 in block
+ *               order.  (A thread walks 256 entries, then n / 256 partials: one region may be the whole mesh.)
+ *   tn_mesh_region, row r of `regions` (72 bytes), over the region's faces f:
+ *     area              SUM2(area_f)
+ *     label, faces      as above; the number of its faces
+ *     mean_temperature  (float)div(SUM2(mul(area_f, (double)tf_f)), area)
+ *     centroid[a]       (float)div(SUM2(mul(area_f, centroid_f,a)), area); with area == 0 the mean and the centroid are the NaN
+ *                       0x7fc00000
+ *     min_temperature, max_temperature   of tf_f;  bounds: min x y z, max x y z over the positions of the region's vertices.  Both
+ *                       in the numbers' order with -0.0 below +0.0, so that they do not depend on any order of evaluation.
+ *     hottest_vertex    the vertex of the region with the highest temperature, compared as numbers (-0.0 == +0.0), the lowest index
+ *                       on a tie; coldest_vertex likewise for the lowest.
+ *   totals (double [2], OVERWRITTEN): [0] SUM2 of area_f over the usable faces in ascending face index (the mesh's area), [1] the
+ *               same over the selected faces.
+ *   counts (device int64 [3], OVERWRITTEN): [0] R — the FULL number; rows at or beyond capacity_regions are not written (0 with
+ *               regions NULL: the sizing call) —, [1] the selected faces, [2] the usable faces.
+ * How: one thread per face writes a 96-byte record (the five products, tf, the face's box, its hottest and coldest corner) and a
+ * copy of the index list in which a face outside the window is invalid; the usable and the selected faces are compacted in order
+ * (count, one-block scan, emit); tn_mesh_components labels the copy; the roots that own a face are numbered and their face and block
+ * counts summed by a second count / scan / emit over the vertices; tn_sort_pairs of (label, face) puts a region's faces side by
+ * side in face order; one thread per 256-block walks its records into a partial, one thread per region walks its partials; the two
+ * totals take the same two steps over the two compacted lists.  workspace: tn_mesh_regions_workspace_bytes(V, T) device bytes,
+ * 8-byte aligned; 0 for counts out of range.  Launches on `stream` only: no allocation, no host synchronisation, no float atomics
+ * (the integer ones are tn_mesh_components' and the sort's), no block waits for another.  The kernels check what they dereference:
+ * a foreign index gives other numbers, never an access outside the arrays.
+ * TN_ERR_NULL: counts or totals is NULL; positions, temperature or the workspace with V > 0 and T > 0; triangles or face_region
+ * with T > 0; regions with capacity_regions > 0; TN_ERR_SHAPE: V < 0 or > 2^31 - 1, T < 0 or 3T > 2^31 - 1, a negative capacity, a
+ * float / int32 pointer not 4-byte aligned, regions / face_area / totals / counts / workspace not 8-byte aligned;
+ * TN_ERR_UNSUPPORTED: a NaN bound; TN_ERR_WORKSPACE: workspace_bytes too small (with V > 0 and T > 0).  All are returned before any
+ * launch.  V == 0 or T == 0: TN_OK, counts and totals are zeroed, face_region filled with -1 and face_area with +0.0 by memsets,
+ * nothing is launched. */
+typedef struct tn_mesh_region {
+    double area;
+    int32_t label;
+    int32_t faces;
+    float mean_temperature;
+    float min_temperature, max_temperature;
+    float centroid[3];
+    float bounds[6];
+    int32_t coldest_vertex, hottest_vertex;
+} tn_mesh_region;
+size_t tn_mesh_regions_workspace_bytes(int64_t num_vertices, int64_t num_triangles);
+int tn_mesh_regions(const float *positions, const float *temperature, const int32_t *triangles, int64_t num_vertices,
+                    int64_t num_triangles, float min_temperature, float max_temperature, tn_mesh_region *regions,
+                    int64_t capacity_regions, int32_t *face_region, double *face_area, int64_t *counts, double *totals,
+                    void *workspace, size_t workspace_bytes, void *stream);
+
 /* ------------------------------------------------------------------------------------------------------
  * Fused forward: Model.forward (collider) + ThermalNerfModel.get_outputs
  * [REF thermal_nerf_model.py:210-275]

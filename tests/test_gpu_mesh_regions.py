@@ -1,0 +1,395 @@
+"""tn_mesh_regions on the device against tests/mesh_regions_reference.py, exactly — every integer and every float bit pattern, no
+tolerance anywhere — into guarded buffers: the literal cases, one region of 1 .. 65 537 faces, the 40 x 40 lattice with its window,
+with an open window and with an empty one, unusable faces scattered through the list, collinear faces and a region of no area, small
+capacities, face_area absent, empty meshes, the error codes, determinism, the Python layer and the command line."""
+from __future__ import annotations
+
+import functools
+import importlib.util
+import json
+import math
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from tests import mesh_regions_reference as R
+from thermo_nerf_amd import _hip
+from thermo_nerf_amd.export import (REGION_DTYPE, ThermalMesh, ThermalRegions, mesh_components, mesh_regions_into,
+                                    mesh_regions_workspace_bytes, read_mesh_ply, regions_mesh, thermal_regions, write_mesh_ply)
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+DEV = "cuda:0"
+F, D = np.float32, np.float64
+GUARD = 96  # elements behind every output buffer that must keep their pattern
+ROW = 72
+FILLS = {torch.int32: -5, torch.float64: -777.0, torch.uint8: 0xEE, torch.int64: -9}
+NAMES = ("positions", "temperature", "triangles", "num_vertices", "num_triangles", "min_temperature", "max_temperature", "regions",
+         "capacity_regions", "face_region", "face_area", "counts", "totals", "workspace", "workspace_bytes", "stream")
+OPEN = (-math.inf, math.inf)
+
+
+def _buffer(elements, dtype):
+    return torch.full((elements + GUARD,), FILLS[dtype], dtype=dtype, device=DEV)
+
+
+def _untouched(buf, start, name):
+    assert bool((buf[start:] == FILLS[buf.dtype]).all()), f"{name} was written at or beyond element {start}"
+
+
+def _device(a):
+    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
+
+
+def raw(mesh, window, cap=None, face_area=True):
+    """tn_mesh_regions into guarded buffers, ``cap`` rows of regions (default: the most the mesh can have; 0: regions is NULL): the
+    buffers and the host copies of counts and totals"""
+    pos, temp, tri = mesh
+    v, t = len(pos), len(tri)
+    cap = min(v // 3, t) if cap is None else cap
+    inputs = [_device(pos), _device(temp), _device(np.ascontiguousarray(tri, dtype=np.int32))]
+    buffers = {"regions": _buffer(cap * ROW, torch.uint8) if cap else None, "face_region": _buffer(t, torch.int32),
+               "face_area": _buffer(t, torch.float64) if face_area else None}
+    counts, totals = _buffer(3, torch.int64), _buffer(2, torch.float64)
+    need = mesh_regions_workspace_bytes(v, t)
+    assert need > 0
+    workspace = _buffer(need, torch.uint8)
+    args = dict(positions=inputs[0].data_ptr() if v else None, temperature=inputs[1].data_ptr() if v else None,
+                triangles=inputs[2].data_ptr() if t else None, num_vertices=v, num_triangles=t, min_temperature=window[0],
+                max_temperature=window[1], capacity_regions=cap, counts=counts.data_ptr(), totals=totals.data_ptr(),
+                workspace=workspace.data_ptr(), workspace_bytes=need, stream=_hip.current_stream(),
+                **{k: _hip.ptr(b) for k, b in buffers.items()})
+    _hip.check(_hip.load().tn_mesh_regions(*[args[k] for k in NAMES]), "tn_mesh_regions")
+    torch.cuda.synchronize()
+    _untouched(counts, 3, "counts")
+    _untouched(totals, 2, "totals")
+    _untouched(workspace, need, "workspace")
+    for name, buf in buffers.items():
+        if buf is not None:
+            _untouched(buf, buf.numel() - GUARD, name)
+    for given, now in zip((pos, temp, np.ascontiguousarray(tri, dtype=np.int32)), inputs):
+        assert np.ascontiguousarray(given).tobytes() == now.cpu().numpy().tobytes(), "an input was written"
+    return {"buffers": buffers, "counts": counts[:3].cpu().numpy(), "totals": totals[:2].cpu().numpy(), "cap": cap}
+
+
+def rows_of(got, n):
+    return np.frombuffer(got["buffers"]["regions"][:n * ROW].cpu().numpy().tobytes(), dtype=REGION_DTYPE)
+
+
+def check(mesh, window, want=None, **kw):
+    """one call compared with the yardstick (or ``want``), bit for bit, on every output it was given"""
+    want = R.regions(*mesh, *window) if want is None else want
+    got = raw(mesh, window, **kw)
+    t = len(mesh[2])
+    assert got["counts"].tolist() == want["counts"].tolist(), "counts"
+    assert R.bits(got["totals"]).tolist() == R.bits(want["totals"]).tolist(), ("totals", got["totals"], want["totals"])
+    assert got["buffers"]["face_region"][:t].cpu().numpy().tobytes() == want["face_region"].tobytes(), "face_region"
+    if got["buffers"]["face_area"] is not None:
+        assert got["buffers"]["face_area"][:t].cpu().numpy().tobytes() == want["face_area"].tobytes(), "face_area"
+    n = min(len(want["regions"]), got["cap"])
+    if n:
+        rows = rows_of(got, n)
+        for name in REGION_DTYPE.names:
+            assert R.bits(rows[name]).tolist() == R.bits(want["regions"][name][:n]).tolist(), name
+        assert rows.tobytes() == want["regions"][:n].tobytes()
+    if got["buffers"]["regions"] is not None:
+        _untouched(got["buffers"]["regions"], n * ROW, "regions")
+    return want, got
+
+
+# ---- the literal cases ----------------------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("name", sorted(R.LITERAL))
+def test_literal_cases_through_the_kernel(name):
+    case = R.LITERAL[name]
+    want, got = check(R.literal_arrays(case), case["window"])
+    n = int(got["counts"][0])
+    mine = {"regions": rows_of(got, n), "counts": got["counts"], "totals": got["totals"],
+            "face_region": got["buffers"]["face_region"][:len(case["triangles"])].cpu().numpy(),
+            "face_area": got["buffers"]["face_area"][:len(case["triangles"])].cpu().numpy()}
+    assert R.literal_mismatch(mine, case["want"]) is None, R.literal_mismatch(mine, case["want"])
+
+
+# ---- one region of n faces ------------------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("faces", [1, 255, 256, 257, 513, 65537])
+def test_one_region_of_exactly_n_faces(faces):
+    pos, tri = R.strip(faces, R.STRIP_SEED)
+    temp = np.random.default_rng(faces).uniform(18.0, 31.0, len(pos)).astype(F)
+    want, got = check((pos, temp, tri), OPEN)
+    assert want["counts"].tolist() == [1, faces, faces] and int(want["regions"]["faces"][0]) == faces
+    assert want["regions"]["area"][0] == want["totals"][0] == want["totals"][1]
+    if faces == 65537:
+        assert faces > 256 * 256, "more than 256 partials: the second level is itself longer than a block"
+        check((pos, temp, tri), (24.0, 25.0))  # the same strip cut into many short regions
+
+
+# ---- the lattice ------------------------------------------------------------------------------------------------------------------------
+
+@functools.lru_cache(maxsize=None)
+def _lattice():
+    pos, tri = R.lattice(40, 40, R.LATTICE_SEED)
+    return pos, R.lattice_temperature(pos, R.LATTICE_SEED), tri
+
+
+@functools.lru_cache(maxsize=None)
+def _lattice_want(window=R.LATTICE_WINDOW):
+    return R.regions(*_lattice(), *window)
+
+
+def test_lattice_with_more_than_a_hundred_regions_of_mixed_size():
+    want, got = check(_lattice(), R.LATTICE_WINDOW, want=_lattice_want())
+    faces = want["regions"]["faces"]
+    assert len(faces) > 100 and faces.max() > 256 and faces.min() == 1
+    check(_lattice(), R.LATTICE_WINDOW, want=_lattice_want(), face_area=False)
+
+
+def test_lattice_with_an_open_window_is_the_components_of_the_whole_mesh_and_an_empty_window_selects_nothing():
+    pos, temp, tri = _lattice()
+    for window in (OPEN, (-math.inf, 1e30), (-1e30, math.inf)):
+        want, got = check(_lattice(), window, want=_lattice_want(OPEN))
+    assert want["counts"].tolist() == [1, len(tri), len(tri)]
+    whole = mesh_components(_device(tri), len(pos))
+    summary = whole.summary.tolist()
+    row = rows_of(got, 1)[0]
+    assert summary[0] == 1 and int(row["label"]) == summary[2] == 0 and int(row["faces"]) == summary[1] == len(tri)
+    assert bool((got["buffers"]["face_region"][:len(tri)] == 0).all())
+    want, got = check(_lattice(), (30.0, 20.0))  # min > max
+    assert got["counts"].tolist() == [0, 0, len(tri)] and got["totals"][1] == 0.0 and got["totals"][0] > 0.0
+    assert bool((got["buffers"]["face_region"][:len(tri)] == -1).all())
+    _untouched(got["buffers"]["regions"], 0, "regions")
+    check(_lattice(), (math.inf, math.inf))
+    check(_lattice(), (24.0, 24.0))
+
+
+def test_unusable_faces_scattered_through_the_list_the_first_and_the_last_included():
+    pos, temp, tri = (a.copy() for a in _lattice())
+    v, t = len(pos), len(tri)
+    rng = np.random.default_rng(17)
+    tri[0], tri[-1] = (v, 1, 2), (5, -1, 6)                  # invalid: first and last face
+    rows = rng.permutation(np.arange(1, t - 1))[:120]
+    tri[rows[:30], 0] = v + rng.integers(0, 5, 30)           # invalid
+    tri[rows[30:60], 1] = -1 - rng.integers(0, 5, 30)
+    tri[rows[60:90], 2] = tri[rows[60:90], 0]                # a repeated index
+    tri[rows[90:120], 1] = tri[rows[90:120], 2]
+    spoiled = rng.permutation(v)[:40]
+    pos[spoiled[:10], rng.integers(0, 3, 10)] = np.nan       # NaN and inf coordinates, NaN and inf temperatures
+    pos[spoiled[10:20], rng.integers(0, 3, 10)] = np.inf
+    pos[spoiled[20:25], 0] = -np.inf
+    temp[spoiled[25:33]] = np.nan
+    temp[spoiled[33:40]] = np.inf
+    for window in (R.LATTICE_WINDOW, OPEN):
+        want, got = check((pos, temp, tri), window)
+        assert want["counts"][2] < t - 120 and want["counts"][0] >= 1 and want["face_region"][0] == want["face_region"][-1] == -1
+        assert want["face_area"][0] == 0.0 and np.isfinite(want["face_area"]).all() and np.isfinite(want["totals"]).all()
+    assert want["counts"][1] == want["counts"][2], "the open window selects every usable face"
+
+
+def test_collinear_faces_are_selected_with_no_area_and_a_region_of_no_area_has_a_nan_mean():
+    # vertices 0 .. 5: a patch with one collinear face among real ones; 6 .. 10 on a line, two collinear faces: a region of area 0
+    pos = np.array([(0, 0, 0), (1, 0, 0), (2, 0, 0), (0, 1, 0), (1, 1, 0), (3, 0, 0), (5, 5, 5), (6, 6, 6), (7, 7, 7), (8, 8, 8), (9.5, 9.5, 9.5)], F)
+    temp = np.array([20, 21, 22, 23, 24, 25, 26, 27, 28, 29, 30], F)
+    tri = np.array([(0, 1, 3), (0, 1, 2), (1, 4, 3), (1, 2, 5), (6, 7, 8), (8, 9, 10)], np.int32)
+    want, got = check((pos, temp, tri), OPEN)
+    assert want["counts"].tolist() == [2, 6, 6] and want["face_region"].tolist() == [0, 0, 0, 0, 1, 1]
+    assert R.bits(want["face_area"]).tolist() == R.bits(np.array([0.5, 0.0, 0.5, 0.0, 0.0, 0.0], D)).tolist()
+    rows = rows_of(got, 2)
+    assert rows["area"].tolist() == [1.0, 0.0] and rows["faces"].tolist() == [4, 2] and rows["label"].tolist() == [0, 6]
+    assert R.bits(rows["mean_temperature"])[1] == 0x7fc00000 and R.bits(rows["centroid"])[1].tolist() == [0x7fc00000] * 3
+    assert rows["min_temperature"][1] == F(27.0) and rows["max_temperature"][1] == F(29.0)
+    assert rows["bounds"][1].tolist() == [5, 5, 5, 9.5, 9.5, 9.5] and (rows["coldest_vertex"][1], rows["hottest_vertex"][1]) == (6, 10)
+    # the collinear faces of region 0 weigh nothing: its mean is that of faces 0 and 2
+    assert rows["mean_temperature"][0] == F(0.5 * float(F(64.0 / 3.0)) + 0.5 * float(F(68.0 / 3.0)))
+    found = thermal_regions(ThermalMesh(_device(pos), torch.zeros((11, 3), dtype=torch.uint8, device=DEV), _device(temp), None, _device(tri)))
+    assert len(found) == 1 and found.num_regions == 2 and found.region_index.tolist() == [0], "a region of no area is always dropped"
+
+
+# ---- capacities, determinism, empty meshes -----------------------------------------------------------------------------------------------
+
+def test_capacities_below_the_result_write_nothing_beyond_them_and_report_the_full_count():
+    want = _lattice_want()
+    r = len(want["regions"])
+    for cap in (0, 1, r - 1, r, r + 7):
+        _, got = check(_lattice(), R.LATTICE_WINDOW, want=want, cap=cap)
+        assert int(got["counts"][0]) == r
+        assert (got["buffers"]["regions"] is None) == (cap == 0)
+
+
+def test_the_same_call_twice_gives_identical_bytes():
+    first, second = raw(_lattice(), R.LATTICE_WINDOW), raw(_lattice(), R.LATTICE_WINDOW)
+    assert first["counts"].tobytes() == second["counts"].tobytes() and first["totals"].tobytes() == second["totals"].tobytes()
+    for name, buf in first["buffers"].items():
+        assert torch.equal(buf, second["buffers"][name]), name
+    pos, tri = R.strip(65537, R.STRIP_SEED)
+    temp = np.full(len(pos), 22.0, F)
+    first, second = raw((pos, temp, tri), OPEN), raw((pos, temp, tri), OPEN)
+    for name, buf in first["buffers"].items():
+        assert torch.equal(buf, second["buffers"][name]), name
+
+
+def test_no_vertices_and_no_triangles():
+    lib = _hip.load()
+    pos, temp, tri = _lattice()
+    for v, t in ((0, 0), (0, 50), (70, 0)):
+        counts, totals = _buffer(3, torch.int64), _buffer(2, torch.float64)
+        face_region, face_area = _buffer(t, torch.int32), _buffer(t, torch.float64)
+        regions = _buffer(4 * ROW, torch.uint8)
+        p, c, i = _device(pos[:max(v, 1)]), _device(temp[:max(v, 1)]), _device(tri[:max(t, 1)])
+        code = lib.tn_mesh_regions(p.data_ptr() if v else None, c.data_ptr() if v else None, i.data_ptr() if t else None, v, t, 20.0, 30.0,
+                                   regions.data_ptr(), 4, face_region.data_ptr() if t else None, face_area.data_ptr() if t else None,
+                                   counts.data_ptr(), totals.data_ptr(), None, 0, _hip.current_stream())
+        torch.cuda.synchronize()
+        assert code == 0, (v, t)
+        assert counts[:3].tolist() == [0, 0, 0] and R.bits(totals[:2].cpu().numpy()).tolist() == [0, 0]
+        assert bool((face_region[:t] == -1).all()) and R.bits(face_area[:t].cpu().numpy()).tolist() == [0] * t
+        for name, buf, n in (("counts", counts, 3), ("totals", totals, 2), ("face_region", face_region, t), ("face_area", face_area, t),
+                             ("regions", regions, 0)):
+            _untouched(buf, n, name)
+        want = R.regions(pos[:v], temp[:v], tri[:t])
+        assert want["counts"].tolist() == [0, 0, 0] and want["totals"].tolist() == [0.0, 0.0] and (want["face_region"] == -1).all()
+    mesh = ThermalMesh(_device(pos[:70]), torch.zeros((70, 3), dtype=torch.uint8, device=DEV), _device(temp[:70]), None,
+                       torch.zeros((0, 3), dtype=torch.int32, device=DEV))
+    found = thermal_regions(mesh, 20.0)
+    assert len(found) == 0 and (found.num_regions, found.selected_faces, found.usable_faces, found.mesh_area) == (0, 0, 0, 0.0)
+    assert len(regions_mesh(mesh, found)) == 0
+
+
+# ---- the error codes ------------------------------------------------------------------------------------------------------------------------
+
+def test_error_codes_with_nothing_written():
+    lib = _hip.load()
+    pos, temp, tri = _lattice()
+    v, t = len(pos), len(tri)
+    inputs = [_device(pos), _device(temp), _device(tri)]
+    regions, face_region, face_area = _buffer(v // 3 * ROW, torch.uint8), _buffer(t, torch.int32), _buffer(t, torch.float64)
+    counts, totals = _buffer(3, torch.int64), _buffer(2, torch.float64)
+    need = mesh_regions_workspace_bytes(v, t)
+    ws = _buffer(need, torch.uint8)
+    good = dict(positions=inputs[0].data_ptr(), temperature=inputs[1].data_ptr(), triangles=inputs[2].data_ptr(), num_vertices=v,
+                num_triangles=t, min_temperature=R.LATTICE_WINDOW[0], max_temperature=R.LATTICE_WINDOW[1], regions=regions.data_ptr(),
+                capacity_regions=v // 3, face_region=face_region.data_ptr(), face_area=face_area.data_ptr(), counts=counts.data_ptr(),
+                totals=totals.data_ptr(), workspace=ws.data_ptr(), workspace_bytes=need, stream=_hip.current_stream())
+
+    def call(**change):
+        args = dict(good, **change)
+        return lib.tn_mesh_regions(*[args[k] for k in NAMES])
+
+    for k in ("positions", "temperature", "triangles", "regions", "face_region", "counts", "totals", "workspace"):
+        assert call(**{k: None}) == -1, k  # TN_ERR_NULL
+    limit = (2 ** 31 - 1) // 3
+    assert call(num_vertices=-1) == -2 and call(num_vertices=2 ** 31) == -2  # TN_ERR_SHAPE
+    assert call(num_triangles=-1) == -2 and call(num_triangles=limit + 1) == -2 and call(capacity_regions=-1) == -2
+    for k in ("positions", "temperature", "triangles", "face_region"):
+        assert call(**{k: good[k] + 2}) == -2, k
+    for k in ("regions", "face_area", "counts", "totals", "workspace"):
+        assert call(**{k: good[k] + 4}) == -2, k
+    assert call(min_temperature=float("nan")) == -3 and call(max_temperature=float("nan")) == -3  # TN_ERR_UNSUPPORTED
+    assert call(workspace_bytes=need - 1) == -4 and call(workspace_bytes=0) == -4  # TN_ERR_WORKSPACE
+    assert lib.tn_mesh_regions_workspace_bytes(-1, 0) == 0 and lib.tn_mesh_regions_workspace_bytes(0, limit + 1) == 0
+    assert lib.tn_mesh_regions_workspace_bytes(2 ** 31, 0) == 0 and lib.tn_mesh_regions_workspace_bytes(2 ** 31 - 1, limit) > 0
+    torch.cuda.synchronize()
+    for name, buf in (("regions", regions), ("face_region", face_region), ("face_area", face_area), ("counts", counts),
+                      ("totals", totals), ("workspace", ws)):
+        _untouched(buf, 0, name)
+    assert call() == 0
+    torch.cuda.synchronize()
+    assert counts[:3].tolist() == _lattice_want()["counts"].tolist()
+
+
+# ---- the Python layer and the command line ---------------------------------------------------------------------------------------------------
+
+def _lattice_mesh():
+    pos, temp, tri = _lattice()
+    rng = np.random.default_rng(23)
+    colors = rng.integers(0, 256, (len(pos), 3)).astype(np.uint8)
+    return ThermalMesh(_device(pos), _device(colors), _device(temp), _device(255 - colors), _device(tri), (14.0, 33.0)), colors
+
+
+def test_thermal_regions_orders_and_filters_the_table_and_regions_mesh_cuts_the_mesh():
+    pos, temp, tri = _lattice()
+    want = _lattice_want()
+    mesh, colors = _lattice_mesh()
+    found = thermal_regions(mesh, *R.LATTICE_WINDOW)
+    assert isinstance(found, ThermalRegions) and found.regions.dtype == REGION_DTYPE
+    order = np.lexsort((want["regions"]["label"], -want["regions"]["area"]))
+    assert (want["regions"]["area"] > 0).all()
+    assert found.region_index.tolist() == order.tolist() and found.regions.tobytes() == want["regions"][order].tobytes()
+    assert (found.num_regions, found.selected_faces, found.usable_faces) == tuple(int(c) for c in want["counts"])
+    assert (found.mesh_area, found.selected_area) == (float(want["totals"][0]), float(want["totals"][1]))
+    assert found.face_region.cpu().numpy().tobytes() == want["face_region"].tobytes() and found.window == R.LATTICE_WINDOW
+    top = thermal_regions(mesh, *R.LATTICE_WINDOW, min_area=1.0, top=5)
+    big = [k for k in order.tolist() if want["regions"]["area"][k] >= 1.0]
+    assert top.region_index.tolist() == big[:5] and len(big) > 5 and top.num_regions == found.num_regions
+    # the faces of the five regions as a mesh of their own
+    part = regions_mesh(mesh, top)
+    keep = np.isin(want["face_region"], big[:5])
+    vertices = np.unique(tri[keep])
+    assert part.triangles.cpu().numpy().tolist() == np.searchsorted(vertices, tri[keep]).tolist()
+    assert part.positions.cpu().numpy().tobytes() == pos[vertices].tobytes() and part.temperature.cpu().numpy().tobytes() == temp[vertices].tobytes()
+    assert part.colors.cpu().numpy().tolist() == colors[vertices].tolist() and part.thermal_colors.cpu().numpy().tolist() == (255 - colors[vertices]).tolist()
+    assert part.temperature_bounds == (14.0, 33.0) and part.normals is None
+    # the raw entry of the Python layer: the sizing call, then exact rows
+    counts, totals = torch.full((3,), -1, dtype=torch.int64, device=DEV), torch.full((2,), -1.0, dtype=torch.float64, device=DEV)
+    face_region = torch.empty((len(tri),), dtype=torch.int32, device=DEV)
+    mesh_regions_into(mesh, *R.LATTICE_WINDOW, counts=counts, totals=totals, face_region=face_region)
+    assert counts.tolist() == want["counts"].tolist()
+    rows = torch.empty((int(counts[0]) * ROW,), dtype=torch.uint8, device=DEV)
+    face_area = torch.empty((len(tri),), dtype=torch.float64, device=DEV)
+    mesh_regions_into(mesh, *R.LATTICE_WINDOW, counts=counts, totals=totals, face_region=face_region, regions=rows, face_area=face_area)
+    assert rows.cpu().numpy().tobytes() == want["regions"].tobytes() and face_area.cpu().numpy().tobytes() == want["face_area"].tobytes()
+    with pytest.raises(ValueError):
+        mesh_regions_into(mesh, *R.LATTICE_WINDOW, counts=counts, totals=totals)  # face_region is missing
+    with pytest.raises(ValueError):
+        mesh_regions_into(mesh, *R.LATTICE_WINDOW, counts=counts, totals=totals, face_region=face_region,
+                          workspace=torch.empty((64,), dtype=torch.uint8, device=DEV))
+
+
+def test_command_line_end_to_end_on_the_lattice_ply(tmp_path, capsys):
+    spec = importlib.util.spec_from_file_location("mesh_regions_tool", os.path.join(ROOT, "tools", "mesh_regions.py"))
+    tool = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(tool)
+    pos, temp, tri = _lattice()
+    want = _lattice_want()
+    mesh, colors = _lattice_mesh()
+    source, report_file, part_file = tmp_path / "lattice.ply", tmp_path / "out" / "regions.json", tmp_path / "regions.ply"
+    write_mesh_ply(source, mesh)
+    lo, hi = R.LATTICE_WINDOW
+    assert tool.main([str(source), "--min-temperature", repr(lo), "--max-temperature", repr(hi), "--top", "4", "--report", str(report_file),
+                      "--output", str(part_file), "--device", DEV]) == 0
+    printed = capsys.readouterr().out
+    report = json.loads(report_file.read_text())
+    order = np.lexsort((want["regions"]["label"], -want["regions"]["area"]))[:4]
+    assert report["window"] == {"min_temperature": lo, "max_temperature": hi} and report["length_scale"] == 1.0
+    assert report["counts"] == {"vertices": len(pos), "faces": len(tri), "usable_faces": int(want["counts"][2]),
+                                "selected_faces": int(want["counts"][1]), "regions": int(want["counts"][0]), "reported_regions": 4}
+    assert (report["mesh_area"], report["selected_area"]) == (float(want["totals"][0]), float(want["totals"][1]))
+    assert report["selected_share"] == float(want["totals"][1]) / float(want["totals"][0])
+    for row, r in zip(report["regions"], order.tolist()):
+        w = want["regions"][r]
+        assert (row["region"], row["label"], row["faces"], row["area"]) == (r, int(w["label"]), int(w["faces"]), float(w["area"]))
+        assert (row["mean_temperature"], row["min_temperature"], row["max_temperature"]) == \
+            (float(w["mean_temperature"]), float(w["min_temperature"]), float(w["max_temperature"]))
+        assert row["centroid"] == [float(c) for c in w["centroid"]]
+        assert row["bounds"] == {"min": [float(c) for c in w["bounds"][:3]], "max": [float(c) for c in w["bounds"][3:]]}
+        for key in ("hottest_vertex", "coldest_vertex"):
+            i = int(w[key])
+            assert row[key] == {"index": i, "position": [float(c) for c in pos[i]], "temperature": float(temp[i])}
+    assert printed.count("\nregion ") == 4 and f"{int(want['counts'][0])} regions, 4 reported" in printed
+    part = read_mesh_ply(part_file)
+    keep = np.isin(want["face_region"], order)
+    vertices = np.unique(tri[keep])
+    assert part["triangles"].tolist() == np.searchsorted(vertices, tri[keep]).tolist()
+    assert part["positions"].tobytes() == pos[vertices].tobytes() and part["temperature"].tobytes() == temp[vertices].tobytes()
+    assert part["colors"].tolist() == colors[vertices].tolist()
+    # thermal colours and a length scale: the same regions, lengths doubled, areas four-fold, the mesh itself unscaled
+    assert tool.main([str(source), "--min-temperature", repr(lo), "--max-temperature", repr(hi), "--top", "4", "--length-scale", "2",
+                      "--report", str(report_file), "--output", str(part_file), "--colors", "thermal", "--device", DEV]) == 0
+    scaled = json.loads(report_file.read_text())
+    assert scaled["mesh_area"] == 4.0 * report["mesh_area"] and scaled["selected_share"] == report["selected_share"]
+    assert [r["area"] for r in scaled["regions"]] == [4.0 * r["area"] for r in report["regions"]]
+    assert scaled["regions"][0]["centroid"] == [2.0 * c for c in report["regions"][0]["centroid"]]
+    again = read_mesh_ply(part_file)
+    assert again["positions"].tobytes() == part["positions"].tobytes()
+    assert again["colors"].tolist() == tool.thermal_bytes(temp[vertices], (14.0, 33.0)).tolist()

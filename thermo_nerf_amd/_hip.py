@@ -86,6 +86,12 @@ class tn_voxel_params(C.Structure):
     _fields_ = [("origin", C.c_float * 3), ("voxel_size", C.c_float), ("dims", C.c_int32 * 3)]
 
 
+class tn_mesh_region(C.Structure):
+    _fields_ = [("area", C.c_double), ("label", C.c_int32), ("faces", C.c_int32), ("mean_temperature", C.c_float),
+                ("min_temperature", C.c_float), ("max_temperature", C.c_float), ("centroid", C.c_float * 3), ("bounds", C.c_float * 6),
+                ("coldest_vertex", C.c_int32), ("hottest_vertex", C.c_int32)]
+
+
 class tn_mesh_params(C.Structure):
     _fields_ = [("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("w2c", C.c_float * 12),
                 ("truncation", C.c_float), ("inv_truncation", C.c_float), ("min_accumulation", C.c_float), ("lo", C.c_float * 3),
@@ -244,6 +250,8 @@ SIGNATURES = {
     "tn_mesh_simplify_workspace_bytes": (_sz, [_i64, _i64]),
     "tn_mesh_simplify": (C.c_int, [_vp] * 5 + [_i64, _i64, C.POINTER(tn_voxel_params)] + [_vp] * 5 + [_i64, _vp, _vp, _i64, _vp, _vp, _vp,
                                    _sz, _vp]),
+    "tn_mesh_regions_workspace_bytes": (_sz, [_i64, _i64]),
+    "tn_mesh_regions": (C.c_int, [_vp, _vp, _vp, _i64, _i64, C.c_float, C.c_float, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "tn_mesh_tile": (_i32, []),
     "tn_mesh_scan_width": (_i32, []),
     "tn_mesh_workspace_bytes": (_sz, [_i32, _i32, _i32]),

@@ -1,6 +1,6 @@
 """Export of a trained scene as 3-D data: a thermal point cloud (positions, colours, degrees per point; optionally without
 statistical outliers, down-sampled to one averaged point per voxel on a stable device sort, and with normals from a k-nearest-neighbour
-search on the device), a thermal triangle mesh (TSDF fusion + surface nets, degrees per vertex; optionally without its small connected components, simplified by vertex clustering, Taubin-smoothed, with vertex normals) and their PLY files."""
+search on the device), a thermal triangle mesh (TSDF fusion + surface nets, degrees per vertex; optionally without its small connected components, simplified by vertex clustering, Taubin-smoothed, with vertex normals), the thermal regions of such a mesh (the patches warmer than X or colder than Y with their area, mean temperature and location) and their PLY files."""
 from .components import (ComponentsInfo, MeshComponents, filter_components, mesh_components,  # noqa: F401
                          mesh_components_workspace_bytes, remove_small_components)
 from .mesh import (MeshExporter, ThermalMesh, camera_pose, grid_dims, mesh_extract, mesh_params, mesh_scan_width,  # noqa: F401
@@ -10,6 +10,8 @@ from .neighbors import (Neighbors, estimate_normals, knn, knn_grid_resolution, k
 from .ply import read_mesh_ply, read_ply, write_mesh_ply, write_ply  # noqa: F401
 from .pointcloud import (PointCloudExporter, ThermalPointCloud, pointcloud_append, pointcloud_params, scan_width,  # noqa: F401
                          subsample, subsample_indices, tile_rays, workspace_bytes, world_transform)
+from .regions import (REGION_DTYPE, ThermalRegions, mesh_regions_into, mesh_regions_workspace_bytes, order_regions,  # noqa: F401
+                      regions_mesh, thermal_regions)
 from .simplify import SimplifyInfo, mesh_simplify_into, mesh_simplify_workspace_bytes, simplify_mesh  # noqa: F401
 from .smooth import (MeshIncidence, mesh_incidence, mesh_incidence_workspace_bytes, smooth_mesh, smooth_positions,  # noqa: F401
                      vertex_normals)
