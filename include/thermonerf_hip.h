@@ -702,6 +702,85 @@ int tn_mesh_regions(const float *positions, const float *temperature, const int3
                     int64_t capacity_regions, int32_t *face_region, double *face_area, int64_t *counts, double *totals,
                     void *workspace, size_t workspace_bytes, void *stream);
 
+/* Orthographic thermogram of an indexed triangle list: a z-buffered rasteriser.  Every pixel of the image has a known size in world
+ * units, the face it shows, its depth, its temperature and (optionally) its colour.  positions [V, 3] floats, temperature [V] floats,
+ * colors [V, 3] bytes (may be NULL), triangles [T, 3] int32, V = num_vertices, T = num_triangles; `view` is read on the HOST.  Every
+ * output is defined to the bit.  add / sub / mul / div below are single correctly rounded fp64 operations, nothing is contracted;
+ * (double) of a float is exact, (double) of an int64 and (float) of a double round to nearest even.
+ *   tn_raster_view: `origin` is the world position of the top-left CORNER of pixel (row 0, col 0) on the image plane; `right`, `down`
+ *     and `forward` are unit and orthogonal with right x down = forward and are TAKEN AS GIVEN; `pixel_size` world units per pixel;
+ *     faces are kept where near <= z <= far (either may be infinite; near > far keeps nothing); width, height in 1 .. 16384; cull 0:
+ *     both sides, 1: faces seen from behind are dropped; reserved: 0, or — for measurements only, it cannot change a bit of the output
+ *     — the small / large box threshold to use in place of tn_mesh_raster_small_box(), 1 .. 16384.
+ *   vertex p:
+ *     q = sub((double)p, origin) per component
+ *     x = div(add(add(mul(qx, rx), mul(qy, ry)), mul(qz, rz)), pixel_size) with r = right; y the same with down; z the same with
+ *         forward, without the division
+ *     X = (int64) of mul(x, 256.0) rounded half to even, Y likewise: fixed point with 8 sub-pixel bits
+ *     RASTERABLE  x, y and z finite, |mul(x, 256.0)| <= 2^29 and |mul(y, 256.0)| <= 2^29 (every edge function below then fits an int64
+ *         exactly)
+ *   face t, indices i0 i1 i2:
+ *     VALID   all three indices in [0, V).   USABLE  valid, the three indices distinct, all three temperatures finite, all three
+ *             vertices rasterable.
+ *     area2   (X1 - X0)(Y2 - Y0) - (Y1 - Y0)(X2 - X0), exact.  area2 > 0: the normal (p1 - p0) x (p2 - p0) points along `forward`, away
+ *             from the viewer.
+ *     DRAWN   usable, area2 != 0, and not (cull == 1 and area2 > 0).
+ *     If area2 < 0 the face's second and third vertex are exchanged, with everything that belongs to them, and area2 is negated: from
+ *     here on area2 > 0 and the vertices are v0 v1 v2.
+ *   coverage of pixel (row j, col i), centre P = (256 i + 128, 256 j + 128):
+ *     E(a, b) = (bx - ax)(Py - ay) - (by - ay)(Px - ax);  w0 = E(v1, v2), w1 = E(v2, v0), w2 = E(v0, v1)  (w0 + w1 + w2 = area2)
+ *     the pixel is COVERED when for every k: wk > 0, or wk == 0 and that edge a -> b is top-left: by - ay < 0, or by - ay == 0 and
+ *     bx - ax > 0.  A pixel centre on an edge shared by two faces, of either winding, belongs to exactly one of them.
+ *   depth and attributes of a covered pixel:
+ *     lk = div((double)wk, (double)area2);  B(a0, a1, a2) = add(add(mul(l0, a0), mul(l1, a1)), mul(l2, a2))
+ *     zp = B(z0, z1, z2); the sample is DROPPED unless near <= zp <= far, compared in fp64
+ *     depth = (float)zp, with -0.0 written as +0.0;  temperature = (float)B((double)t0, (double)t1, (double)t2)
+ *     colour channel c = floor(add(B((double)c0, (double)c1, (double)c2), 0.5)) clamped to [0, 255]
+ *   winner: key = (ord(depth) << 32) | t, ord the order-preserving map of fp32 bits to uint32 (b -> ~b with the sign bit set, b |
+ *     0x80000000 without), t the face's index in the list AS GIVEN.  The pixel shows the sample with the smallest key: the nearest
+ *     surface, and on equal fp32 depth the lowest face index.  A minimum does not depend on the order in which it is taken.
+ *   outputs, row-major [height, width], each of the four pixel arrays may be NULL:
+ *     pixel_face (int32)   the face index; -1 on an empty pixel
+ *     pixel_depth, pixel_temperature (float)   the NaN 0x7fc00000 on an empty pixel
+ *     pixel_colors (uint8 [H, W, 3])   0 on an empty pixel; must be NULL when colors is NULL
+ *     counts (device int64 [3], OVERWRITTEN)   [0] covered pixels, [1] drawn faces, [2] usable faces
+ *     stats (device double [3], OVERWRITTEN)   [0] SUM2, as tn_mesh_regions defines it (blocks of 256), over ALL pixels in row-major
+ *         order of (double)temperature, an empty pixel contributing +0.0; [1], [2] the minimum and the maximum of (double)temperature
+ *         over the covered pixels in the numbers' order with -0.0 below +0.0; +inf and -inf without a covered pixel.
+ * How: one thread per face transforms its vertices, classifies it, writes a 72-byte record (the fixed-point corners, the three
+ * depths, area2, the indices after the exchange) and clips its box of pixel centres to the image.  A face whose box is at most
+ * tn_mesh_raster_small_box() pixels on both sides is rasterised by that thread, straight into a uint64 key plane in the workspace
+ * with a 64-bit integer atomic minimum; a plain load of the current key skips the atomic when the sample cannot win (a minimum
+ * only falls).  The faces with a larger box are compacted in face order (count, one-block scan, emit) and swept in 16 x 16 pixel
+ * tiles by blocks of 256 threads, a tile being skipped whole when one edge function is negative at its four corners.  A resolve
+ * pass, one thread per pixel, decodes the key, recomputes the barycentrics from the record and writes the four arrays and one
+ * partial per 256 pixels; one block finishes SUM2, the extremes and the covered count.  workspace:
+ * tn_mesh_rasterize_workspace_bytes(T, width, height) device bytes, 8-byte aligned; 0 for arguments out of range.  Launches on
+ * `stream` only: no allocation, no host synchronisation, no float atomics, no block waits for another.  The kernels check what they
+ * dereference: a foreign index gives an unusable face, never an access outside the arrays.
+ * TN_ERR_NULL: view, counts or stats is NULL; positions, temperature or the workspace with V > 0 and T > 0; triangles with T > 0;
+ * colors with pixel_colors; TN_ERR_SHAPE: V < 0 or > 2^31 - 1, T < 0 or 3T > 2^31 - 1, width or height outside 1 .. 16384,
+ * pixel_size not a finite positive number, a non-finite origin or axis component, a float / int32 pointer not 4-byte aligned, counts /
+ * stats / workspace not 8-byte aligned; TN_ERR_UNSUPPORTED: a NaN near or far, cull outside {0, 1}, reserved outside 0 .. 16384;
+ * TN_ERR_WORKSPACE: workspace_bytes too small (with V > 0 and T > 0).  All are returned before any launch, in the siblings' order:
+ * NULL of view / counts / stats, SHAPE of the numbers, UNSUPPORTED, NULL of the arrays, SHAPE of the alignment, WORKSPACE.
+ * V == 0 or T == 0: TN_OK, the pixel arrays are filled with their empty values, counts are zeroed, stats = (+0.0, +inf, -inf). */
+typedef struct tn_raster_view {
+    double origin[3];
+    double right[3], down[3], forward[3];
+    double pixel_size;
+    double near, far;
+    int32_t width, height;
+    int32_t cull;
+    int32_t reserved;
+} tn_raster_view;
+int32_t tn_mesh_raster_small_box(void);
+size_t tn_mesh_rasterize_workspace_bytes(int64_t num_triangles, int32_t width, int32_t height);
+int tn_mesh_rasterize(const float *positions, const float *temperature, const uint8_t *colors, const int32_t *triangles,
+                      int64_t num_vertices, int64_t num_triangles, const tn_raster_view *view, int32_t *pixel_face, float *pixel_depth,
+                      float *pixel_temperature, uint8_t *pixel_colors, int64_t *counts, double *stats, void *workspace,
+                      size_t workspace_bytes, void *stream);
+
 /* ------------------------------------------------------------------------------------------------------
  * Fused forward: Model.forward (collider) + ThermalNerfModel.get_outputs
  * [REF thermal_nerf_model.py:210-275]

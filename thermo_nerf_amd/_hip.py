@@ -92,6 +92,12 @@ class tn_mesh_region(C.Structure):
                 ("coldest_vertex", C.c_int32), ("hottest_vertex", C.c_int32)]
 
 
+class tn_raster_view(C.Structure):
+    _fields_ = [("origin", C.c_double * 3), ("right", C.c_double * 3), ("down", C.c_double * 3), ("forward", C.c_double * 3),
+                ("pixel_size", C.c_double), ("near", C.c_double), ("far", C.c_double), ("width", C.c_int32), ("height", C.c_int32),
+                ("cull", C.c_int32), ("reserved", C.c_int32)]
+
+
 class tn_mesh_params(C.Structure):
     _fields_ = [("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("w2c", C.c_float * 12),
                 ("truncation", C.c_float), ("inv_truncation", C.c_float), ("min_accumulation", C.c_float), ("lo", C.c_float * 3),
@@ -252,6 +258,9 @@ SIGNATURES = {
                                    _sz, _vp]),
     "tn_mesh_regions_workspace_bytes": (_sz, [_i64, _i64]),
     "tn_mesh_regions": (C.c_int, [_vp, _vp, _vp, _i64, _i64, C.c_float, C.c_float, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "tn_mesh_raster_small_box": (_i32, []),
+    "tn_mesh_rasterize_workspace_bytes": (_sz, [_i64, _i32, _i32]),
+    "tn_mesh_rasterize": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i64, C.POINTER(tn_raster_view), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "tn_mesh_tile": (_i32, []),
     "tn_mesh_scan_width": (_i32, []),
     "tn_mesh_workspace_bytes": (_sz, [_i32, _i32, _i32]),

@@ -1,6 +1,6 @@
 """Export of a trained scene as 3-D data: a thermal point cloud (positions, colours, degrees per point; optionally without
 statistical outliers, down-sampled to one averaged point per voxel on a stable device sort, and with normals from a k-nearest-neighbour
-search on the device), a thermal triangle mesh (TSDF fusion + surface nets, degrees per vertex; optionally without its small connected components, simplified by vertex clustering, Taubin-smoothed, with vertex normals), the thermal regions of such a mesh (the patches warmer than X or colder than Y with their area, mean temperature and location) and their PLY files."""
+search on the device), a thermal triangle mesh (TSDF fusion + surface nets, degrees per vertex; optionally without its small connected components, simplified by vertex clustering, Taubin-smoothed, with vertex normals), the thermal regions of such a mesh (the patches warmer than X or colder than Y with their area, mean temperature and location), orthographic thermograms of a mesh (a scaled, distortion-free image through a z-buffered device rasteriser: the face, depth, temperature and colour of every pixel) and their PLY files."""
 from .components import (ComponentsInfo, MeshComponents, filter_components, mesh_components,  # noqa: F401
                          mesh_components_workspace_bytes, remove_small_components)
 from .mesh import (MeshExporter, ThermalMesh, camera_pose, grid_dims, mesh_extract, mesh_params, mesh_scan_width,  # noqa: F401
@@ -15,5 +15,7 @@ from .regions import (REGION_DTYPE, ThermalRegions, mesh_regions_into, mesh_regi
 from .simplify import SimplifyInfo, mesh_simplify_into, mesh_simplify_workspace_bytes, simplify_mesh  # noqa: F401
 from .smooth import (MeshIncidence, mesh_incidence, mesh_incidence_workspace_bytes, smooth_mesh, smooth_positions,  # noqa: F401
                      vertex_normals)
+from .thermogram import (RasterView, Thermogram, fit_view, mesh_raster_small_box, mesh_rasterize_into,  # noqa: F401
+                         mesh_rasterize_workspace_bytes, mesh_thermogram, place_view, view_axes)
 from .voxel import (sort_pairs, sort_pairs_workspace_bytes, sort_tile, voxel_downsample, voxel_downsample_into,  # noqa: F401
                     voxel_downsample_workspace_bytes, voxel_grid, voxel_params)
