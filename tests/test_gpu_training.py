@@ -787,14 +787,18 @@ def test_tape_free_step_equals_the_taped_step(kind, S, hw, split):
         assert rel(g1[n], g) <= 2e-4, f"{n}: rel {rel(g1[n], g):.2e} (|g| {g.norm().item():.2e})"
 
 
-@pytest.mark.parametrize("hw", [(12, 12), (7, 5), (1, 3)])  # 64-sample multiples, a ragged last tile, fewer samples than a tile
-@pytest.mark.parametrize("S", [48, 192, 5])
-def test_kept_base_output_equals_the_tape_and_the_recomputing_backward(S, hw):
-    """config.backward_bf16_pieces (round 5): tn_field_bwd_fused's split form 2 — the heads' 64 x 64 products as six products of
-    exact bf16 pieces — against form 1 (fp32 MFMA) on the same inputs, and
-    config.store_base_output (round 5): tn_field_fwd_train's optional base_out [N,16] holds the rows tn_field_fwd_taped writes
-    as `bo` (same MFMA chain: bit for bit), and tn_field_bwd_fused's head launches reading them give the gradients of the launches
-    that recompute mlp_base from the hash features (fp32 summation order of mlp_base's products differs between the two)."""
+FIELD_TRAIN_FORMS = ((True, 1), (False, 1), (True, 2), (True, "jac"))
+
+
+def field_train_forms(S, hw, pos=None, forms=FIELD_TRAIN_FORMS):
+    """The call plumbing around tn_field_fwd_train / tn_field_bwd_fused on the "stress" model with R = hw rays x S samples:
+    tn_field_fwd_taped (the tape to compare with), tn_field_fwd_train three times (base rows kept | nothing optional | base rows
+    and the position Jacobian kept, each into buffers with a guard row behind them) and one tn_field_bwd_fused per entry of
+    ``forms`` = (head launches read the kept base rows?, form 1 | 2 | "jac": form 2 with the position gradient from the
+    forward's Jacobian).  ``pos`` [R * S, 3] device positions (default: uniformly random inside and outside the unit box).
+    Returns a namespace of everything written; ``res[(stored, form)]`` holds the gradients of one backward call."""
+    from types import SimpleNamespace
+
     from thermo_nerf_amd import _hip
 
     gm, sd, ocfg, o, d, jit, cam, batch = _train_setup("stress", S, R_hw=hw)
@@ -802,7 +806,9 @@ def test_kept_base_output_equals_the_tape_and_the_recomputing_backward(S, hw):
     R = o.shape[0]
     N = R * S
     dd, cc = d.to(DEV), cam.to(DEV).reshape(-1).to(torch.int32)
-    pos = (torch.rand(N, 3, generator=torch.Generator().manual_seed(5)) * 3 - 1.5).to(DEV)
+    if pos is None:
+        pos = (torch.rand(N, 3, generator=torch.Generator().manual_seed(5)) * 3 - 1.5).to(DEV)
+    assert pos.shape == (N, 3) and pos.is_contiguous()
     fld = gm.field.c_struct(prepare=True, dense=False)
     f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=DEV)
     st = _hip.current_stream()
@@ -818,20 +824,17 @@ def test_kept_base_output_equals_the_tape_and_the_recomputing_backward(S, hw):
     _hip.check(lib.tn_field_fwd_train(fld, pos.data_ptr(), ray_bias.data_ptr(), R, S, enc_t.data_ptr(), sel_t.data_ptr(),
                                       dens_t.data_ptr(), rgb_t.data_ptr(), th_t.data_ptr(), base.data_ptr(), None, st), "tn_field_fwd_train")
     torch.cuda.synchronize()
-    assert torch.equal(base[:N], bo) and bool((base[N] == 7.0).all())
+    # without the optional store
     rgb_n, th_n = f32(N, 3), f32(N, 1)
     _hip.check(lib.tn_field_fwd_train(fld, pos.data_ptr(), ray_bias.data_ptr(), R, S, enc_t.data_ptr(), sel_t.data_ptr(),
                                       dens_t.data_ptr(), rgb_n.data_ptr(), th_n.data_ptr(), None, None, st), "tn_field_fwd_train")
-    assert torch.equal(rgb_n, rgb_t) and torch.equal(th_n, th_t)  # the optional store changes nothing else
-    # ... nor does the optional position Jacobian (config.store_position_jacobian), another instantiation of the kernel
+    # with the optional position Jacobian (config.store_position_jacobian), another instantiation of the kernel
     jac = torch.full(((N + 63) // 64 * 64 + 1, 96), 7.0, device=DEV)
-    enc_j, base_j = torch.empty_like(enc_t), torch.empty_like(base)
+    enc_j, base_j, rgb_j, th_j = torch.empty_like(enc_t), torch.empty_like(base), f32(N, 3), f32(N, 1)
     _hip.check(lib.tn_field_fwd_train(fld, pos.data_ptr(), ray_bias.data_ptr(), R, S, enc_j.data_ptr(), sel_t.data_ptr(),
-                                      dens_t.data_ptr(), rgb_n.data_ptr(), th_n.data_ptr(), base_j.data_ptr(), jac.data_ptr(), st),
+                                      dens_t.data_ptr(), rgb_j.data_ptr(), th_j.data_ptr(), base_j.data_ptr(), jac.data_ptr(), st),
                "tn_field_fwd_train")
     torch.cuda.synchronize()
-    assert torch.equal(rgb_n, rgb_t) and torch.equal(th_n, th_t) and torch.equal(base_j[:N], bo) and bool((jac[-1] == 7.0).all())
-    assert torch.equal(enc_j.view(-1, 16, 64, 2)[: N // 64], enc_t.view(-1, 16, 64, 2)[: N // 64])
 
     g = torch.Generator().manual_seed(9)
     g_rgb, g_th, g_dens = (torch.randn(N, 3, generator=g) * 1e-3).to(DEV), (torch.randn(N, generator=g) * 1e-3).to(DEV), \
@@ -842,7 +845,7 @@ def test_kept_base_output_equals_the_tape_and_the_recomputing_backward(S, hw):
     ws = torch.empty(lib.tn_field_bwd_fused_workspace_bytes(R, S), dtype=torch.uint8, device=DEV)
     res = {}
     # form 2: the heads' 64 x 64 products as six bf16-piece products; "jac": the position gradient from the forward's Jacobian
-    for stored, form in ((True, 1), (False, 1), (True, 2), (True, "jac")):
+    for stored, form in forms:
         from_jac, form = (form == "jac"), (2 if form == "jac" else form)
         grads = {n: torch.zeros_like(p) for n, p in gm.named_parameters()}
         gr = _hip.tn_field_grads()
@@ -858,6 +861,27 @@ def test_kept_base_output_equals_the_tape_and_the_recomputing_backward(S, hw):
         torch.cuda.synchronize()
         res[(stored, "jac" if from_jac else form)] = dict({nme + sfx: grads[nme + sfx] for nme in names.values() for sfx in (".weight", ".bias") if nme + sfx in grads},
                            g_enc=g_enc, g_ray=g_ray, g_pos=g_pos)
+    return SimpleNamespace(gm=gm, fld=fld, R=R, S=S, N=N, pos=pos, bo=bo, base=base, sel=sel_t, rgb_t=rgb_t, th_t=th_t, rgb_n=rgb_n,
+                           th_n=th_n, rgb_j=rgb_j, th_j=th_j, enc_t=enc_t, enc_j=enc_j, base_j=base_j, jac=jac, res=res)
+
+
+@pytest.mark.parametrize("hw", [(12, 12), (7, 5), (1, 3)])  # 64-sample multiples, a ragged last tile, fewer samples than a tile
+@pytest.mark.parametrize("S", [48, 192, 5])
+def test_kept_base_output_equals_the_tape_and_the_recomputing_backward(S, hw):
+    """config.backward_bf16_pieces (round 5): tn_field_bwd_fused's split form 2 — the heads' 64 x 64 products as six products of
+    exact bf16 pieces — against form 1 (fp32 MFMA) on the same inputs, and
+    config.store_base_output (round 5): tn_field_fwd_train's optional base_out [N,16] holds the rows tn_field_fwd_taped writes
+    as `bo` (same MFMA chain: bit for bit), and tn_field_bwd_fused's head launches reading them give the gradients of the launches
+    that recompute mlp_base from the hash features (fp32 summation order of mlp_base's products differs between the two).
+    (The position gradient of these forms against an fp64 reference, sample by sample: tests/test_gpu_position_gradient.py.)"""
+    f = field_train_forms(S, hw)
+    N, bo, base, jac, res = f.N, f.bo, f.base, f.jac, f.res
+    assert torch.equal(base[:N], bo) and bool((base[N] == 7.0).all())
+    assert torch.equal(f.rgb_n, f.rgb_t) and torch.equal(f.th_n, f.th_t)  # the optional store changes nothing else
+    # ... nor does the optional position Jacobian (config.store_position_jacobian), another instantiation of the kernel
+    assert torch.equal(f.rgb_j, f.rgb_t) and torch.equal(f.th_j, f.th_t) and torch.equal(f.base_j[:N], bo) and bool((jac[-1] == 7.0).all())
+    assert torch.equal(f.enc_j.view(-1, 16, 64, 2)[: N // 64], f.enc_t.view(-1, 16, 64, 2)[: N // 64])
+
     for k, want in res[(False, 1)].items():
         for other in ((True, 1), (True, 2), (True, "jac")):
             if want.norm().item() == 0.0:
@@ -1284,6 +1308,8 @@ def test_ray_gradients_match_autograd_oracle(kind, contraction, sh_grad):
     _, _, want = T.loss_and_grads(sd, o, d, cam, batch, ocfg, jit)
     # the position gradient is a sum over 16 levels of (feature differences x level scale up to 2047): the fine levels
     # dominate and cancel.  Yardstick: the fp32 oracle itself is 3e-3 .. 1e-2 away from its fp64 run on these cases.
+    # (The tight check, kernel by kernel and sample by sample against a cell-exact fp64 reference, at a counted number of
+    # roundings: tests/test_gpu_position_gradient.py.)
     assert rel(od.grad, want["__origins__"]) <= 2e-2, rel(od.grad, want["__origins__"])
     assert rel(dd.grad, want["__directions__"]) <= 2e-2, rel(dd.grad, want["__directions__"])
     # and the parameter gradients are unchanged by asking for ray gradients

@@ -439,8 +439,14 @@ __device__ __forceinline__ void hash_encode_pipelined(const G &g, float px, floa
     hash_encode_pipelined_raw<NL, LG, ND, GP>(g, px, py, pz, [&](int l, const HashTaps &t, const float2 (&f)[8]) { emit(l, hash_blend(t, f)); }, base);
 }
 // hash_blend's features AND their derivatives with respect to the three interpolation offsets (jac[c] = d features / d offset c;
-// times the level's scale = d features / d normalised position).  The differences are the ones the lerps form anyway.
+// times the level's scale = d features / d normalised position).
+// The FEATURES keep hash_blend's two-instruction lerp fmaf(o, a - b, b), bit for bit.  The SLOPES do not reuse its differences:
+// that form rounds (a - b) with weight o on both corners, so towards o = 1 (one ulp below a grid plane) the floor corner b
+// carries an error of o eps |b| where the polynomial weighs it with 1 - o — single entries left the bound
+// K eps (o |a| + (1 - o) |b|) that the recomputing backward (encode_level_grad) keeps.  The slopes interpolate as
+// fmaf(o, a, fmaf(-o, b, b)) = o a + (1 - o) b: two instructions as well, each corner's rounding weighted like the corner.
 // Hashed levels only (the training path never reads the dense re-layout).
+__device__ __forceinline__ float lerp_w(float a, float b, float o) { return fmaf(o, a, fmaf(-o, b, b)); }
 __device__ __forceinline__ float2 hash_blend_jac(const HashTaps &t, const float2 (&f)[8], float2 (&jac)[3]) {
     float2 r;
 #define TN_BLEND_JAC(c)                                                                                              \
@@ -448,14 +454,13 @@ __device__ __forceinline__ float2 hash_blend_jac(const HashTaps &t, const float2
         const float d03 = f[0].c - f[3].c, d12 = f[1].c - f[2].c, d56 = f[5].c - f[6].c, d47 = f[4].c - f[7].c;      \
         const float f03 = fmaf(t.ox, d03, f[3].c), f12 = fmaf(t.ox, d12, f[2].c);                                    \
         const float f56 = fmaf(t.ox, d56, f[6].c), f47 = fmaf(t.ox, d47, f[7].c);                                    \
-        const float e0312 = f03 - f12, e4756 = f47 - f56;                                                            \
-        const float f0312 = fmaf(t.oy, e0312, f12), f4756 = fmaf(t.oy, e4756, f56);                                  \
-        const float ez = f0312 - f4756;                                                                              \
-        r.c = fmaf(t.oz, ez, f4756);                                                                                 \
-        const float dx_hi = fmaf(t.oy, d03 - d12, d12), dx_lo = fmaf(t.oy, d47 - d56, d56);                          \
-        jac[0].c = fmaf(t.oz, dx_hi - dx_lo, dx_lo);                                                                 \
-        jac[1].c = fmaf(t.oz, e0312 - e4756, e4756);                                                                 \
-        jac[2].c = ez;                                                                                               \
+        const float f0312 = fmaf(t.oy, f03 - f12, f12), f4756 = fmaf(t.oy, f47 - f56, f56);                          \
+        r.c = fmaf(t.oz, f0312 - f4756, f4756);                                                                      \
+        jac[0].c = lerp_w(lerp_w(d03, d12, t.oy), lerp_w(d47, d56, t.oy), t.oz);                                     \
+        const float c03 = lerp_w(f[0].c, f[3].c, t.ox), c12 = lerp_w(f[1].c, f[2].c, t.ox);                          \
+        const float c56 = lerp_w(f[5].c, f[6].c, t.ox), c47 = lerp_w(f[4].c, f[7].c, t.ox);                          \
+        jac[1].c = lerp_w(c03 - c12, c47 - c56, t.oz);                                                               \
+        jac[2].c = lerp_w(c03, c12, t.oy) - lerp_w(c47, c56, t.oy);                                                  \
     }
     TN_BLEND_JAC(x)
     TN_BLEND_JAC(y)

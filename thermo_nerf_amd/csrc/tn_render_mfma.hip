@@ -1209,7 +1209,7 @@ __global__ void __launch_bounds__(kBlock, 2) field_fwd_taped_kernel(TapedArgs a)
             float2 *et = reinterpret_cast<float2 *>(a.enc) + ps * (16 * 64) + lane;
             if (JAC) {
                 // camera-pose optimisation (round 5): the corner values are in registers here — the backward's position gradient
-                // re-read all of them (100 M table reads per S=192 step); 18 more vector instructions per level and 24 more
+                // re-read all of them (100 M table reads per S=192 step); about 50 more vector instructions per level and 24 more
                 // bytes per (sample, level) give it d features / d position instead
                 float2 *jt = reinterpret_cast<float2 *>(a.jac) + ps * (16 * 3 * 64) + lane;
                 hash_encode_pipelined_raw<L16, TN_TRAIN_JAC_LG, 0, TN_TRAIN_GATHER_PRIO>(a.g, px, py, pz, [&](int l, const HashTaps &t, const float2 (&fc)[8]) {
