@@ -781,6 +781,132 @@ int tn_mesh_rasterize(const float *positions, const float *temperature, const ui
                       float *pixel_temperature, uint8_t *pixel_colors, int64_t *counts, double *stats, void *workspace,
                       size_t workspace_bytes, void *stream);
 
+/* Ray queries against an indexed triangle list: a linear bounding-volume hierarchy (LBVH) built on the device, and a traversal that
+ * gives every ray the face it meets first, where, and the temperature and colour there.  positions [V, 3] floats, temperature [V]
+ * floats, colors [V, 3] bytes (may be NULL), triangles [T, 3] int32, V = num_vertices, T = num_triangles.  Every output is defined to
+ * the bit, and WITHOUT reference to the tree.  add / sub / mul / div below are single correctly rounded fp64 operations, nothing is
+ * contracted; (double) of a float is exact, (float) of a double rounds to nearest even.  min and max of floats are taken in the
+ * numbers' order with -0.0 below +0.0.
+ *   face t, indices i0 i1 i2:
+ *     USABLE  all three indices in [0, V) and distinct, the nine coordinates finite, the three temperatures finite (tn_mesh_rasterize's
+ *             USABLE without "rasterable").
+ *     box     lo = min, hi = max of its three fp32 corners per axis: exact.
+ *
+ * THE BLOB (tn_mesh_bvh_build writes it, tn_mesh_raycast reads it; tn_mesh_bvh_bytes(T) = 64 + 64 ceil(4 T / 64) + 64 max(T - 1, 0)
+ * device bytes, 64-byte aligned; little endian):
+ *   header, 64 bytes   uint32 magic 0x56424e54; int32 version 1; int32 num_faces = T; int32 num_usable = U; int32 num_unusable = T - U;
+ *                      int32 num_nodes = max(U - 1, 0); int32 root; int32 depth; float lo[3], hi[3]: the EXTENT, min of lo and max of hi
+ *                      over the usable faces (+inf and -inf when U == 0); two zero int32.
+ *                      root: U >= 2: 0, the internal node 0; U == 1: -1, the leaf 0; U == 0: INT32_MIN, there is nothing to meet.
+ *                      depth: the height of the root (the internal nodes on the longest way down to a leaf); 0 when U < 2.
+ *   faces              int32 [T], padded with zeros to a multiple of 64 bytes: the face indices in LEAF ORDER — ascending key, equal
+ *                      keys in ascending face index (tn_sort_pairs over 31 bits).  The first U are the usable faces, leaf k is faces[k].
+ *   nodes              [max(T - 1, 0)] x 64 bytes, the first num_nodes are the tree, the rest are zero:
+ *                      float lo[2][3], hi[2][3]: the boxes of child 0 and of child 1; int32 child[2]: c >= 0 is the internal node c,
+ *                      c < 0 the leaf ~c; int32 level: the node's height, 1 + the larger of its children's, a leaf being 0; a zero int32.
+ *                      The box of a leaf is its face's; the box of an internal node is the min / max of its two children's boxes.
+ *   key of a face      usable: the 30-bit Morton code of q, bit 3 b + 2 - k of the code = bit b of q_k (k = 0 x, 1 y, 2 z), with
+ *                      c_k = mul(add((double)lo_k, (double)hi_k), 0.5) the box centre, w_k = sub((double)HI_k, (double)LO_k) the
+ *                      extent's width, q_k = 0 when w_k == 0, else floor(mul(div(sub(c_k, (double)LO_k), w_k), 1024.0)) clamped to
+ *                      [0, 1023].  Unusable: 2^30, above every code.
+ *   tree               Karras's radix tree (Maximizing parallelism in the construction of BVHs, octrees and k-d trees, 2012) over the
+ *                      first U entries of the leaf order with delta(i, j) = clz32(key_i ^ key_j) for different keys and
+ *                      32 + clz32(i ^ j) for equal ones (i, j positions in the leaf order): all keys are distinct, the tree is unique.
+ *                      Internal node i covers the positions first .. last, one of them i; child 0 covers first .. split, child 1
+ *                      split + 1 .. last; a child that covers one position is that leaf, otherwise child 0 is node split and child 1
+ *                      node split + 1.
+ *   DEPTH BOUND        tn_mesh_bvh_depth_bound() = 61.  Proof: delta(first, last) of a node is the length of the common prefix of the
+ *                      (key, position) strings it covers, and it grows strictly from a node to its internal child.  Between different
+ *                      keys it is clz32 of a non-zero number below 2^30: one of the 30 values 2 .. 31.  Between equal keys it is
+ *                      32 + clz32 of a non-zero number below 2^31: one of the 31 values 33 .. 63.  A way down passes at most 30 + 31
+ *                      internal nodes.
+ *   The blob is deterministic: two builds of one mesh are byte-equal.
+ * How it is built: one thread per face classifies it and folds its box into the extent (a wave's minimum first, then integer atomic
+ * min / max on the order-preserving bit patterns of the floats; no float atomics); one thread per face computes its key; tn_sort_pairs
+ * writes the leaf order into the blob; one thread per internal node finds its range and split; then tn_mesh_bvh_depth_bound()
+ * launches fit the boxes bottom-up: in launch p a node whose two children were done BEFORE the launch (a leaf always is; an internal
+ * child carries a level in 1 .. p - 1) takes their boxes and the level p, so level = height.  Launch boundaries carry the data
+ * between blocks: no block hands data to another inside a launch, nothing waits, there is no fence.  workspace:
+ * tn_mesh_bvh_workspace_bytes(T) device bytes, 8-byte aligned.  Launches on `stream` only, no allocation, no host synchronisation.
+ * tn_mesh_bvh_build: TN_ERR_NULL: bvh; TN_ERR_SHAPE: V < 0 or > 2^31 - 1, T < 0 or 3T > 2^31 - 1; TN_ERR_NULL: with T > 0 triangles
+ * or the workspace, with T > 0 and V > 0 positions or temperature; TN_ERR_SHAPE: a float / int32 pointer not 4-byte aligned, bvh not
+ * 64-byte aligned, the workspace not 8-byte aligned; TN_ERR_WORKSPACE: bvh_bytes or workspace_bytes too small.  All are returned
+ * before any launch.  T == 0: TN_OK, the header alone is written.  Both size functions are 0 for T out of range.
+ *
+ * THE CAST.  origins, directions [N, 3] floats, ray_t_max [N] floats or NULL, N = num_rays, 3N <= 2^31 - 1; `params` is read on the HOST:
+ * 0 <= t_min, t_max may be +inf (t_min > t_max meets nothing); cull 0: both sides, 1: faces seen from behind are dropped; mode
+ * TN_RAYCAST_CLOSEST or TN_RAYCAST_ANY.
+ *   ray i     USABLE when its six floats are finite and its direction is not (0, 0, 0).  o, d = (double) of them; directions are NOT
+ *             normalised, t is in units of the direction.  t_end = t_max, or with ray_t_max: r = (double)ray_t_max[i],
+ *             t_end = r < t_max ? r : t_max (a NaN leaves t_max).  An unusable ray is a miss.
+ *   slab of the ray against a box lo .. hi, per axis k:
+ *             d_k == 0: the axis PASSES iff lo_k <= o_k <= hi_k, and gives no bound.  Otherwise inv_k = div(1, d_k),
+ *             a = mul(sub(lo_k, o_k), inv_k), b = mul(sub(hi_k, o_k), inv_k), near_k = min(a, b), far_k = max(a, b).
+ *             enter = max(t_min, near_k ...), exit = min(t_end, far_k ...), s = mul(enter, 1 - 2^-32).
+ *             The box PASSES iff every zero axis passes and s <= exit.  (The slack does real work: rays through the vertices and
+ *             edge midpoints of an axis-aligned cube graze boxes of zero thickness, where the rounding of a and b can put enter
+ *             above exit by an ulp; without the slack thousands of true hits of such a scene fail the test, with it none.)
+ *   face test, Moeller-Trumbore in fp64 with p0 p1 p2 = (double) of the corners, dot(a, b) = add(add(mul(ax, bx), mul(ay, by)),
+ *             mul(az, bz)), cross(a, b) = (sub(mul(ay, bz), mul(az, by)), sub(mul(az, bx), mul(ax, bz)), sub(mul(ax, by), mul(ay, bx))):
+ *             e1 = sub(p1, p0), e2 = sub(p2, p0), pv = cross(d, e2), det = dot(e1, pv).  det == 0 is a miss.  det = -dot(d, n) with
+ *             n = (p1 - p0) x (p2 - p0): det < 0 is a face whose normal points along the ray, away from the viewer — SEEN FROM
+ *             BEHIND in tn_mesh_rasterize's sense (its area2 > 0) — and cull == 1 drops it.
+ *             tv = sub(o, p0), u = div(dot(tv, pv), det), qv = cross(tv, e1), v = div(dot(d, qv), det), t = div(dot(e2, qv), det).
+ *   HIT       a usable face with u >= 0, v >= 0, add(u, v) <= 1, t_min <= t <= t_end, whose own box passes with s <= t.
+ *   winner    the HIT with the smallest t in fp64, then the lowest face index in the list AS GIVEN.
+ * Why the tree cannot change the output: the computed slab bounds are monotone under box inclusion — inv_k is the ray's, sub and mul
+ * round monotonically, so a larger box has near_k no larger and far_k no smaller on every axis, a zero axis that passes the smaller
+ * box passes the larger, and mul(enter, 1 - 2^-32) is monotone in enter.  The box of every ancestor of a face contains the face's box
+ * (exact fp32 min / max), so when a face is a HIT every ancestor passes and its s is at most the face's s, which is at most t.  A
+ * traversal that skips a node when it does not pass, or when its s exceeds the best t so far, therefore never skips the winner — nor
+ * any HIT with the winner's t, so the index tie-break is safe as well.
+ *   outputs, each array may be NULL:
+ *     hit_face (int32 [N])   the winner's face index; -1 on a miss
+ *     hit_t (float [N])      (float)t; the NaN 0x7fc00000 on a miss
+ *     hit_uv (float [N, 2])  (float)u, (float)v; the NaN on a miss
+ *     hit_temperature (float [N])   (float)add(add(mul(sub(sub(1, u), v), T0), mul(u, T1)), mul(v, T2)) with Tk = (double)temperature
+ *                            of the face's corner k; the NaN on a miss
+ *     hit_colors (uint8 [N, 3])   per channel floor(add(add(add(mul(sub(sub(1, u), v), c0), mul(u, c1)), mul(v, c2)), 0.5)) clamped to
+ *                            [0, 255], tn_mesh_rasterize's rounding; 0 on a miss; needs colors
+ *     hit_any (uint8 [N])    TN_RAYCAST_ANY only, and then the ONLY array written: 1 iff some HIT exists (the traversal stops at the
+ *                            first it finds)
+ *     counts (device int64 [4], OVERWRITTEN, CLOSEST only)   [0] rays that hit, [1] usable rays, [2] usable faces (the header's),
+ *                            [3] rays that reached the limit of the traversal stack
+ *     stats (device double [3], OVERWRITTEN, CLOSEST only; needs hit_temperature)   as tn_mesh_rasterize defines them: [0] SUM2
+ *                            (blocks of 256) over ALL rays in ray order of (double)hit_temperature, a miss contributing +0.0;
+ *                            [1], [2] the minimum and the maximum over the hits; +inf and -inf without a hit.
+ * How: one ray per lane, blocks of one wave.  A node is one 64-byte fetch that decides both children; the nearer child (the smaller
+ * s) is descended first and the other pushed on a stack of 64 entries per ray in LDS (16 KiB per wave).  A way down pushes at most
+ * one entry per internal node: 61 <= 64, so counts[3] is 0 for every blob this library builds.  The kernel never writes past its
+ * stack: a ray that reaches the limit does not descend that subtree and is counted.  The kernel checks what it dereferences: a
+ * header that does not carry the magic, the version and T is a tree without a face; node and leaf numbers are compared against
+ * num_nodes and T, face and vertex indices against T and V; the number of steps is bounded by 2 T + 2, which a tree never reaches.  A
+ * foreign blob gives other numbers, never an access outside the arrays.  The counts are integer atomic sums of the waves' ballots; one
+ * block finishes the statistics from hit_temperature.  Launches on `stream` only, no allocation, no host synchronisation, no float
+ * atomics, no block waits for another.
+ * tn_mesh_raycast: TN_ERR_NULL: params or bvh; TN_ERR_SHAPE: V, T out of range (as above), N < 0 or 3N > 2^31 - 1;
+ * TN_ERR_UNSUPPORTED: t_min or t_max a NaN, t_min < 0, cull outside {0, 1}, an unknown mode; TN_ERR_NULL: positions, temperature or
+ * triangles with V > 0 and T > 0; origins or directions with N > 0; and in CLOSEST mode colors with hit_colors, hit_temperature with
+ * stats and N > 0; TN_ERR_SHAPE: a float / int32 pointer not 4-byte aligned, counts / stats not 8-byte aligned, bvh not 64-byte
+ * aligned; TN_ERR_WORKSPACE: bvh_bytes < tn_mesh_bvh_bytes(T).  All are returned before any launch, in the siblings' order. */
+#define TN_RAYCAST_CLOSEST 0
+#define TN_RAYCAST_ANY 1
+typedef struct tn_raycast_params {
+    double t_min, t_max;
+    int32_t cull;
+    int32_t mode;
+} tn_raycast_params;
+int32_t tn_mesh_bvh_depth_bound(void);
+size_t tn_mesh_bvh_bytes(int64_t num_triangles);
+size_t tn_mesh_bvh_workspace_bytes(int64_t num_triangles);
+int tn_mesh_bvh_build(const float *positions, const float *temperature, const int32_t *triangles, int64_t num_vertices,
+                      int64_t num_triangles, void *bvh, size_t bvh_bytes, void *workspace, size_t workspace_bytes, void *stream);
+int tn_mesh_raycast(const float *positions, const float *temperature, const uint8_t *colors, const int32_t *triangles,
+                    int64_t num_vertices, int64_t num_triangles, const void *bvh, size_t bvh_bytes, const float *origins,
+                    const float *directions, const float *ray_t_max, int64_t num_rays, const tn_raycast_params *params,
+                    int32_t *hit_face, float *hit_t, float *hit_uv, float *hit_temperature, uint8_t *hit_colors, uint8_t *hit_any,
+                    int64_t *counts, double *stats, void *stream);
+
 /* ------------------------------------------------------------------------------------------------------
  * Fused forward: Model.forward (collider) + ThermalNerfModel.get_outputs
  * [REF thermal_nerf_model.py:210-275]

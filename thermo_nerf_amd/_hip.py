@@ -98,6 +98,13 @@ class tn_raster_view(C.Structure):
                 ("cull", C.c_int32), ("reserved", C.c_int32)]
 
 
+class tn_raycast_params(C.Structure):
+    _fields_ = [("t_min", C.c_double), ("t_max", C.c_double), ("cull", C.c_int32), ("mode", C.c_int32)]
+
+
+TN_RAYCAST_CLOSEST, TN_RAYCAST_ANY = 0, 1
+
+
 class tn_mesh_params(C.Structure):
     _fields_ = [("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("w2c", C.c_float * 12),
                 ("truncation", C.c_float), ("inv_truncation", C.c_float), ("min_accumulation", C.c_float), ("lo", C.c_float * 3),
@@ -261,6 +268,11 @@ SIGNATURES = {
     "tn_mesh_raster_small_box": (_i32, []),
     "tn_mesh_rasterize_workspace_bytes": (_sz, [_i64, _i32, _i32]),
     "tn_mesh_rasterize": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i64, C.POINTER(tn_raster_view), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "tn_mesh_bvh_depth_bound": (_i32, []),
+    "tn_mesh_bvh_bytes": (_sz, [_i64]),
+    "tn_mesh_bvh_workspace_bytes": (_sz, [_i64]),
+    "tn_mesh_bvh_build": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _vp, _sz, _vp, _sz, _vp]),
+    "tn_mesh_raycast": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i64, _vp, _sz, _vp, _vp, _vp, _i64, C.POINTER(tn_raycast_params)] + [_vp] * 9),
     "tn_mesh_tile": (_i32, []),
     "tn_mesh_scan_width": (_i32, []),
     "tn_mesh_workspace_bytes": (_sz, [_i32, _i32, _i32]),

@@ -1,6 +1,6 @@
 """Export of a trained scene as 3-D data: a thermal point cloud (positions, colours, degrees per point; optionally without
 statistical outliers, down-sampled to one averaged point per voxel on a stable device sort, and with normals from a k-nearest-neighbour
-search on the device), a thermal triangle mesh (TSDF fusion + surface nets, degrees per vertex; optionally without its small connected components, simplified by vertex clustering, Taubin-smoothed, with vertex normals), the thermal regions of such a mesh (the patches warmer than X or colder than Y with their area, mean temperature and location), orthographic thermograms of a mesh (a scaled, distortion-free image through a z-buffered device rasteriser: the face, depth, temperature and colour of every pixel) and their PLY files."""
+search on the device), a thermal triangle mesh (TSDF fusion + surface nets, degrees per vertex; optionally without its small connected components, simplified by vertex clustering, Taubin-smoothed, with vertex normals), the thermal regions of such a mesh (the patches warmer than X or colder than Y with their area, mean temperature and location), orthographic thermograms of a mesh (a scaled, distortion-free image through a z-buffered device rasteriser: the face, depth, temperature and colour of every pixel), ray queries against a mesh (a bounding-volume hierarchy built on the device and a traversal kernel: the view of a pinhole camera pixel for pixel, the temperature and the surface point behind a pixel, whether a point is visible from a camera) and their PLY files."""
 from .components import (ComponentsInfo, MeshComponents, filter_components, mesh_components,  # noqa: F401
                          mesh_components_workspace_bytes, remove_small_components)
 from .mesh import (MeshExporter, ThermalMesh, camera_pose, grid_dims, mesh_extract, mesh_params, mesh_scan_width,  # noqa: F401
@@ -10,6 +10,9 @@ from .neighbors import (Neighbors, estimate_normals, knn, knn_grid_resolution, k
 from .ply import read_mesh_ply, read_ply, write_mesh_ply, write_ply  # noqa: F401
 from .pointcloud import (PointCloudExporter, ThermalPointCloud, pointcloud_append, pointcloud_params, scan_width,  # noqa: F401
                          subsample, subsample_indices, tile_rays, workspace_bytes, world_transform)
+from .raycast import (CameraThermogram, CameraView, MeshBVH, RayHits, build_mesh_bvh, camera_rays, mesh_bvh_bytes,  # noqa: F401
+                      mesh_bvh_depth_bound, mesh_bvh_workspace_bytes, mesh_camera_thermogram, mesh_raycast, mesh_raycast_into,
+                      visible_from)
 from .regions import (REGION_DTYPE, ThermalRegions, mesh_regions_into, mesh_regions_workspace_bytes, order_regions,  # noqa: F401
                       regions_mesh, thermal_regions)
 from .simplify import SimplifyInfo, mesh_simplify_into, mesh_simplify_workspace_bytes, simplify_mesh  # noqa: F401
