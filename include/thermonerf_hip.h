@@ -907,6 +907,81 @@ int tn_mesh_raycast(const float *positions, const float *temperature, const uint
                     int32_t *hit_face, float *hit_t, float *hit_uv, float *hit_temperature, uint8_t *hit_colors, uint8_t *hit_any,
                     int64_t *counts, double *stats, void *stream);
 
+/* The nearest point of the mesh to every query point: the other walk through tn_mesh_bvh_build's blob.  The mesh arrays, V, T, bvh and
+ * bvh_bytes are the ray cast's; points [N, 3] floats, point_temperature [N] floats or NULL, N = num_points, 3N <= 2^31 - 1; `params` is
+ * read on the HOST: max_distance = R >= 0, which may be +inf; reserved: write 0.  Every output is defined to the bit, and WITHOUT
+ * reference to the tree, in the ray cast's conventions: add / sub / mul / div / sqrt are single correctly rounded fp64 operations,
+ * nothing is contracted, (double) of a float is exact, (float) of a double rounds to nearest even, dot and cross are the ray cast's.
+ *   point i   USABLE when its three floats are finite; Q = (double) of them.  Faces are USABLE as for the ray cast.
+ *   bound of a box lo .. hi (fp32) against Q:
+ *             g_k = max(sub((double)lo_k, Q_k), sub(Q_k, (double)hi_k), 0) per axis, b = add(add(mul(g0, g0), mul(g1, g1)), mul(g2, g2)).
+ *   closest point of a face, p0 p1 p2 = (double) of its corners, lo .. hi its own box: up to four CANDIDATES (C, u, v), in this order:
+ *     interior  e1 = sub(p1, p0), e2 = sub(p2, p0), n = cross(e1, e2), nn = dot(n, n).  Left out when nn == 0.  w = sub(Q, p0),
+ *               u = div(dot(cross(w, e2), n), nn), v = div(dot(cross(e1, w), n), nn).  A candidate iff u >= 0, v >= 0 and
+ *               add(u, v) <= 1; then C_k = add(add(p0_k, mul(u, e1_k)), mul(v, e2_k)).
+ *     edges     of a segment a -> b: ab = sub(b, a), den = dot(ab, ab), s = 0 when den == 0, else div(dot(sub(Q, a), ab), den); then
+ *               s = 1 when s > 1, s = +0.0 unless s > 0 (a -0.0 becomes +0.0).  C_k = add(a_k, mul(s, ab_k)).
+ *               p0 -> p1 with (u, v) = (s, 0); p0 -> p2 with (0, s); p1 -> p2 with (sub(1, s), s).
+ *     clamp     every candidate's C is clamped per axis into the face's own box: C_k = lo_k when C_k < lo_k, hi_k when C_k > hi_k
+ *               (exact).  r_k = sub(Q_k, C_k), d2 = add(add(mul(r0, r0), mul(r1, r1)), mul(r2, r2)).
+ *     The face's closest point is the candidate with the smallest d2, the first in the order above on a tie.  A usable face without
+ *     area (collinear or coincident corner positions under distinct indices) has nn == 0 and is the segment or the point its edges
+ *     are: no division by zero is taken, no NaN can arise (every operand is finite and no product of them leaves the fp64 range).
+ *   winner    among the usable faces with d2 <= R2, R2 = mul(R, R): the smallest d2 in fp64, then the lowest face index in the list AS
+ *             GIVEN.
+ * Why the tree cannot change the output: after the clamp C_k lies in [lo_k, hi_k], and sub is monotone and odd, so on every axis
+ * |r_k| >= g_k of the face's own box — where Q_k < lo_k: sub(Q_k, C_k) <= sub(Q_k, lo_k) = -sub(lo_k, Q_k) <= 0; likewise above hi_k;
+ * in between g_k = 0.  mul and add are monotone, and d2 and b add in the same order: d2 >= b of the face's own box.  The box of every
+ * ancestor contains the face's box (exact fp32 min / max), a larger box has g_k no larger on every axis, so b is monotone under box
+ * inclusion: every ancestor's b <= the face's own b <= d2.  A traversal that skips a node only when its b > the best d2 so far,
+ * strictly, or when b > R2, therefore never skips the winner — nor a face that ties with it, so the index tie-break is safe as well.
+ *   outputs, each array may be NULL:
+ *     closest_face (int32 [N])        the winner's face index; -1 when the point is unusable, there is no usable face, or none lies
+ *                                     within R
+ *     closest_distance (float [N])    (float)sqrt(d2)
+ *     closest_point (float [N, 3])    (float)C, the clamped candidate
+ *     closest_uv (float [N, 2])       (float)u, (float)v
+ *     closest_temperature (float [N]), closest_colors (uint8 [N, 3])   from (u, v) exactly as hit_temperature and hit_colors from theirs;
+ *                                     closest_colors needs colors
+ *     difference (float [N])          (float)sub((double)point_temperature[i], (double)closest_temperature[i]), from the ROUNDED
+ *                                     float: the point minus the surface.  Needs point_temperature and closest_temperature.  The NaN
+ *                                     0x7fc00000 whenever the result is a NaN (either is one).
+ *     Without a face the floats are the NaN 0x7fc00000 and the colours 0.
+ *     counts (device int64 [4], OVERWRITTEN)   [0] points with a face, [1] usable points, [2] usable faces (the header's), [3] points
+ *                                     that reached the limit of the traversal stack
+ *     stats (device double [8], OVERWRITTEN; needs closest_distance)   sums are SUM2 (blocks of 256, as tn_mesh_rasterize defines it)
+ *                                     over ALL points in order of x = (double) of the rounded float output, +0.0 where the point has no
+ *                                     value (the output is a NaN): [0] of closest_distance, [1] of mul(x, x) of it, [2], [3] its minimum
+ *                                     and maximum over the points that have one, in the numbers' order with -0.0 below +0.0; [4] .. [7]
+ *                                     the same of difference.  +inf and -inf where no point has the value; [4] .. [7] are (+0.0, +0.0,
+ *                                     +inf, -inf) with difference NULL.
+ * How: one point per lane, blocks of one wave.  A node is one 64-byte fetch that gives both children's b; a child with b > the best
+ * d2 so far (R2 until a face is found) is skipped, of two that stay the one with the smaller b is descended first and the other is
+ * pushed on a stack of 64 entries per point in LDS ([entry][lane], 16 KiB per wave, as the ray cast's).  A popped entry is tested
+ * again, against the best d2 by then: an internal node through the b of its two children, a leaf through the b of its face's own box,
+ * before any of the face's arithmetic.  The depth bound 61 <= 64: counts[3] is 0 for every blob this library builds, and
+ * the kernel never writes past its stack — a point that reaches the limit does not descend that subtree and is counted.  The kernel
+ * checks what it dereferences as the ray cast does: the header's magic, version and T; node and leaf numbers against num_nodes and T, face and vertex indices
+ * against T and V; at most 2 T + 2 steps.  A foreign or zeroed blob gives other numbers or no face, never an access outside the
+ * arrays.  The counts are integer atomic sums of the waves' ballots; one block finishes the statistics from closest_distance and
+ * difference.  Launches on `stream` only, no allocation, no host synchronisation, no float atomics, no block waits for another.
+ * tn_mesh_closest: TN_ERR_NULL: params or bvh; TN_ERR_SHAPE: V, T out of range (as above), N < 0 or 3N > 2^31 - 1;
+ * TN_ERR_UNSUPPORTED: max_distance a NaN or < 0; TN_ERR_NULL: positions, temperature or triangles with V > 0 and T > 0; points with
+ * N > 0; colors with closest_colors; closest_temperature with difference, and point_temperature with difference and N > 0;
+ * closest_distance with stats; TN_ERR_SHAPE: a float / int32 pointer not 4-byte aligned, counts / stats not 8-byte aligned, bvh not
+ * 64-byte aligned;
+ * TN_ERR_WORKSPACE: bvh_bytes < tn_mesh_bvh_bytes(T).  All are returned before any launch, in the siblings' order.  N == 0 or T == 0:
+ * TN_OK, counts and stats are written, every point is without a face. */
+typedef struct tn_closest_params {
+    double max_distance;
+    int32_t reserved[2];
+} tn_closest_params;
+int tn_mesh_closest(const float *positions, const float *temperature, const uint8_t *colors, const int32_t *triangles,
+                    int64_t num_vertices, int64_t num_triangles, const void *bvh, size_t bvh_bytes, const float *points,
+                    const float *point_temperature, int64_t num_points, const tn_closest_params *params, int32_t *closest_face,
+                    float *closest_distance, float *closest_point, float *closest_uv, float *closest_temperature,
+                    uint8_t *closest_colors, float *difference, int64_t *counts, double *stats, void *stream);
+
 /* ------------------------------------------------------------------------------------------------------
  * Fused forward: Model.forward (collider) + ThermalNerfModel.get_outputs
  * [REF thermal_nerf_model.py:210-275]

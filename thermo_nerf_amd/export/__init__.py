@@ -1,6 +1,7 @@
 """Export of a trained scene as 3-D data: a thermal point cloud (positions, colours, degrees per point; optionally without
 statistical outliers, down-sampled to one averaged point per voxel on a stable device sort, and with normals from a k-nearest-neighbour
-search on the device), a thermal triangle mesh (TSDF fusion + surface nets, degrees per vertex; optionally without its small connected components, simplified by vertex clustering, Taubin-smoothed, with vertex normals), the thermal regions of such a mesh (the patches warmer than X or colder than Y with their area, mean temperature and location), orthographic thermograms of a mesh (a scaled, distortion-free image through a z-buffered device rasteriser: the face, depth, temperature and colour of every pixel), ray queries against a mesh (a bounding-volume hierarchy built on the device and a traversal kernel: the view of a pinhole camera pixel for pixel, the temperature and the surface point behind a pixel, whether a point is visible from a camera) and their PLY files."""
+search on the device), a thermal triangle mesh (TSDF fusion + surface nets, degrees per vertex; optionally without its small connected components, simplified by vertex clustering, Taubin-smoothed, with vertex normals), the thermal regions of such a mesh (the patches warmer than X or colder than Y with their area, mean temperature and location), orthographic thermograms of a mesh (a scaled, distortion-free image through a z-buffered device rasteriser: the face, depth, temperature and colour of every pixel), ray queries against a mesh (a bounding-volume hierarchy built on the device and a traversal kernel: the view of a pinhole camera pixel for pixel, the temperature and the surface point behind a pixel, whether a point is visible from a camera), the nearest point of a mesh to any point through the same hierarchy (distances between clouds and meshes, and the per-vertex difference in degrees Celsius between two surveys as a mesh of its own) and their PLY files."""
+from .closest import ClosestPoints, MeshDifference, mesh_closest, mesh_closest_into, mesh_difference  # noqa: F401
 from .components import (ComponentsInfo, MeshComponents, filter_components, mesh_components,  # noqa: F401
                          mesh_components_workspace_bytes, remove_small_components)
 from .mesh import (MeshExporter, ThermalMesh, camera_pose, grid_dims, mesh_extract, mesh_params, mesh_scan_width,  # noqa: F401
