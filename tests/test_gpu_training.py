@@ -2,7 +2,12 @@
 CPU oracle (oracle/hotpath.py + oracle/training.py), then the whole step (outputs, losses, every parameter gradient).
 
 Tolerances (written per test): the kernels are fp32 with a different summation order than torch's (tiled dots, atomics),
-so gradients are compared in relative L2 norm per tensor; values pointwise."""
+so gradients are compared in relative L2 norm per tensor; values pointwise.
+
+The two halves of the hash encoding's adjoint are also held to fp64 references of their own, element by element: the position
+gradient sample by sample (tests/position_gradient_reference.py, tests/test_gpu_position_gradient.py) and the table gradient
+entry by entry, with inputs whose sums are exact in fp32 (tests/table_gradient_reference.py, tests/test_gpu_table_gradient.py)
+— a whole-table L2 norm is dominated by the crowded coarse entries and would not see a lost record at a fine level."""
 import copy
 import ctypes as C
 
