@@ -7,7 +7,10 @@ so gradients are compared in relative L2 norm per tensor; values pointwise.
 The two halves of the hash encoding's adjoint are also held to fp64 references of their own, element by element: the position
 gradient sample by sample (tests/position_gradient_reference.py, tests/test_gpu_position_gradient.py) and the table gradient
 entry by entry, with inputs whose sums are exact in fp32 (tests/table_gradient_reference.py, tests/test_gpu_table_gradient.py)
-— a whole-table L2 norm is dominated by the crowded coarse entries and would not see a lost record at a fine level."""
+— a whole-table L2 norm is dominated by the crowded coarse entries and would not see a lost record at a fine level.  The per-ray
+kernels above them (tn_ray_render_bwd, tn_weights_bwd, tn_composite_bwd, the distortion and interlevel losses, tn_image_losses) are
+held element by element to tests/ray_losses_reference.py by tests/test_gpu_ray_losses.py: exact on dyadic and single-interval
+inputs, bounded by counted roundings elsewhere."""
 import copy
 import ctypes as C
 

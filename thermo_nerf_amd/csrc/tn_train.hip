@@ -1983,7 +1983,9 @@ __global__ void __launch_bounds__(kBlock) interlevel_kernel(InterlevelArgs a) {
         lo = min(max(lo, 0), p - 1);
         int hi = upper_bound(edges + 1, p, cr[i + 1]);       // searchsorted(ends = cp[1:], right)
         hi = min(max(hi, 0), p - 1);
-        const float w_outer = cum[hi + 1] - cum[lo];
+        // >= 0: the envelope of weights is; the wave scan groups the same addends differently from lane to lane, so over a run
+        // of zero weights cum is not monotone, and -1 ulp here against w = 0 (den = 1e-7) was a coefficient of order 1
+        const float w_outer = fmaxf(cum[hi + 1] - cum[lo], 0.0f);
         const float wi = wr[i];
         const float d = fmaxf(wi - w_outer, 0.0f);
         const float den = wi + 1.0e-7f;
