@@ -982,6 +982,97 @@ int tn_mesh_closest(const float *positions, const float *temperature, const uint
                     float *closest_distance, float *closest_point, float *closest_uv, float *closest_temperature,
                     uint8_t *closest_colors, float *difference, int64_t *counts, double *stats, void *stream);
 
+/* The measured thermal photos projected onto points of the mesh: what the cameras MEASURED at every point, from how many photos, how
+ * far these agree, and where the model differs.  The third reader of tn_mesh_bvh_build's blob.  positions, temperature, triangles, V, T,
+ * bvh and bvh_bytes are the ray cast's (temperature decides which faces are USABLE and is not read otherwise); points [P, 3] floats,
+ * normals [P, 3] floats or NULL (no facing test: cos = 1), point_temperature [P] floats or NULL, P = num_points, 3P <= 2^31 - 1;
+ * cameras: K = num_cameras <= 2^31 - 1 DEVICE records of 64 bytes, c2w the row-major 3 x 4 camera-to-world in tn_generate_rays'
+ * convention (the camera looks along its -z, +y is up), fx fy cx cy in pixels; images [K, H, W] DEVICE bytes, the 8-bit thermal
+ * photos, all of one size; `params` is read on the HOST: t_lo, t_hi the temperatures of byte 0 and byte 255 (finite, in any order),
+ * 0 < min_cos <= 1, near >= 0, width = W and height = H in 2 .. 16384, two_sided 0 or not, reserved: write 0.  Every output is
+ * defined to the bit, in the ray cast's conventions: add / sub / mul / div / sqrt are single correctly rounded fp64 operations unless
+ * marked fp32, nothing is contracted, (double) of a float or a byte is exact, (float) of a double rounds to nearest even, dot is the
+ * ray cast's dot, -x is exact.
+ *   point i    USABLE when its three floats are finite and, with normals, its normal's three floats are finite and not all zero.
+ *              p = its floats, n = (double) of its normal.  An unusable point is seen by no camera.
+ *   camera k   USABLE when its sixteen floats are finite and fx > 0, fy > 0.  An unusable camera is skipped.
+ *   PAIR (i, k) of a usable point and a usable camera, the clauses in this order; the pair is ACCEPTED when none rejects it:
+ *     1 ray    e = (c2w[3], c2w[7], c2w[11]) fp32, d32_j = fp32 sub(p_j, e_j), d = (double)d32: the ray (e, d32) is the one
+ *              visible_from casts at the point, t = 1 is the point.
+ *     2 depth  xc = dot(c0, d), yc = dot(c1, d), zc = dot(c2, d) with c_j = (double)(c2w[j], c2w[4 + j], c2w[8 + j]), column j of the
+ *              rotation; z = -zc.  Rejected (BEHIND) unless z > 0 and z >= near.
+ *     3 pixel  u = add(mul(fx, div(xc, z)), cx), v = sub(cy, mul(fy, div(yc, z))): the centre of pixel (row r, column c) is
+ *              (u, v) = (c + 0.5, r + 0.5), as tn_generate_rays places it.  Rejected (OUTSIDE) unless 0.5 <= u <= W - 0.5 and
+ *              0.5 <= v <= H - 0.5: the hull of the pixel centres; nothing is extrapolated into the half-pixel border.
+ *     4 facing dist2 = dot(d, d), dist = sqrt(dist2); cos = div(-dot(n, d), mul(dist, sqrt(dot(n, n)))), |cos| with two_sided; 1
+ *              without normals.  Rejected (FACING) unless cos >= min_cos: equality is inside.
+ *     5 occlusion   the pair has REACHED the occlusion test.  The ray o = (double)e, direction d, 0 <= t <= 1 - 2^-10, no culling,
+ *              against the usable faces exactly as THE CAST defines a HIT (the ray is unusable, and meets nothing, when d32 is not
+ *              finite or is (0, 0, 0)).  Rejected (HIDDEN) when some HIT exists.
+ *     6 sample a = sub(u, 0.5), x0 = min((int)floor(a), W - 2), fa = sub(a, x0); b = sub(v, 0.5), y0 = min((int)floor(b), H - 2),
+ *              fb = sub(b, y0).  With B(r, c) = (double)images[k][r][c]: top = add(B(y0, x0), mul(fa, sub(B(y0, x0 + 1), B(y0, x0)))),
+ *              bottom = add(B(y0 + 1, x0), mul(fa, sub(B(y0 + 1, x0 + 1), B(y0 + 1, x0)))), s = add(top, mul(fb, sub(bottom, top))),
+ *              Tk = add(t_lo, mul(div(s, 255), sub(t_hi, t_lo))).
+ *     7 weight w = div(cos, dist2): up to the camera's constant the reciprocal of the surface area one pixel covers there — a
+ *              near, frontal photo outweighs a far, oblique one.
+ *   fusion of point i over its accepted pairs in ASCENDING k, from sw = swt = +0.0: sw = add(sw, w), swt = add(swt, mul(w, Tk)),
+ *              views += 1; the first accepted pair sets lo = hi = Tk and best = k with its w, a later one sets lo = Tk when Tk < lo,
+ *              hi = Tk when Tk > hi, and best = k when its w > the best's w, strictly: the lower index wins a tie.
+ *   outputs, each array may be NULL:
+ *     measured (float [P])      (float)div(swt, sw); the NaN 0x7fc00000 when views == 0 (or the quotient is a NaN)
+ *     views (int32 [P])         the accepted pairs of the point
+ *     best_camera (int32 [P])   best; -1 when views == 0
+ *     spread (float [P])        (float)sub(hi, lo): how far the photos disagree — a hot spot that moves with the viewpoint is a
+ *                               reflection; the NaN when views == 0
+ *     difference (float [P])    (float)sub((double)point_temperature[i], (double)measured_i) from the ROUNDED float measured_i, whether
+ *                               or not the measured array is given: model minus measurement.  Needs point_temperature.  The NaN
+ *                               0x7fc00000 whenever the result is a NaN (either is one).
+ *     counts (device int64 [6], OVERWRITTEN)   [0] points with views > 0, [1] usable points, [2] usable cameras, [3] pairs that
+ *                               reached the occlusion test, [4] pairs accepted, [5] pairs whose walk reached the limit of the
+ *                               traversal stack
+ *     stats (device double [8], OVERWRITTEN)   sums are SUM2 (blocks of 256, as tn_mesh_rasterize defines it) over ALL points in
+ *                               order of x = (double) of the rounded float output, +0.0 where the output is a NaN: [0] of
+ *                               difference, [1] of mul(x, x) of it, [2], [3] its minimum and maximum over the points that have
+ *                               one (in the numbers' order, -0.0 below +0.0); [4] of spread, [5] the maximum of spread; [6] of
+ *                               measured; [7] +0.0, reserved.  Each is taken from its output array: with that array NULL, or no
+ *                               point with the value, a sum is +0.0, a minimum +inf and a maximum -inf.
+ * Why the order is fixed: one lane owns one point and walks the cameras in ascending k with sw, swt, lo, hi and best in registers.
+ * No sum is shared between lanes, so there is no atomic and no reduction whose order a schedule could change: two calls, on any
+ * device state, write the same bytes.
+ * How: one point per lane, blocks of one wave.  The camera's record is addressed by k alone, so a wave reads it once.  Clauses 2 - 4
+ * cost a few dozen operations and come first; only the pairs they leave walk the tree, with the ray cast's own slab and face test
+ * (one definition in the source) in its any-hit traversal: a node is one 64-byte fetch that decides both children, the nearer
+ * child (the smaller s) first, the other on a stack of 64 entries per lane in LDS ([entry][lane], 16 KiB per wave), the walk ends
+ * at the first HIT.  Which HIT ends it cannot matter: clause 5 asks only whether one exists, and THE CAST's proof shows that the
+ * traversal skips no HIT.  The kernel checks what it dereferences as the ray cast does; x0, y0 are also clamped at 0 (never
+ * taken inside the hull).  The counts are integer atomic sums of the waves' sums; one block finishes the statistics from the
+ * difference, spread and measured arrays.  Launches on `stream` only, no allocation, no host synchronisation, no float atomics,
+ * no block waits for another.
+ * tn_mesh_project: TN_ERR_NULL: params or bvh; TN_ERR_SHAPE: V, T out of range (as above), P < 0 or 3P > 2^31 - 1, K < 0 or
+ * > 2^31 - 1, width or height outside 2 .. 16384; TN_ERR_UNSUPPORTED: min_cos not in (0, 1], near < 0, t_lo or t_hi not finite (a NaN
+ * fails each); TN_ERR_NULL: positions, temperature or triangles with V > 0 and T > 0; points with P > 0; cameras or images with K > 0;
+ * point_temperature with difference and P > 0; TN_ERR_SHAPE: a float / int32 pointer or cameras not 4-byte aligned, counts / stats not
+ * 8-byte aligned, bvh not 64-byte aligned; TN_ERR_WORKSPACE: bvh_bytes < tn_mesh_bvh_bytes(T).  All are returned before any launch,
+ * in the siblings' order.  P == 0 or K == 0 or T == 0: TN_OK, counts and stats are written; without a camera no point is seen,
+ * without a face nothing hides one. */
+typedef struct tn_project_camera {
+    float c2w[12];
+    float fx, fy, cx, cy;
+} tn_project_camera;
+typedef struct tn_project_params {
+    double t_lo, t_hi;
+    double min_cos;
+    double near;
+    int32_t width, height;
+    int32_t two_sided;
+    int32_t reserved;
+} tn_project_params;
+int tn_mesh_project(const float *positions, const float *temperature, const int32_t *triangles, int64_t num_vertices,
+                    int64_t num_triangles, const void *bvh, size_t bvh_bytes, const float *points, const float *normals,
+                    const float *point_temperature, int64_t num_points, const tn_project_camera *cameras, const uint8_t *images,
+                    int64_t num_cameras, const tn_project_params *params, float *measured, int32_t *views, int32_t *best_camera,
+                    float *spread, float *difference, int64_t *counts, double *stats, void *stream);
+
 /* ------------------------------------------------------------------------------------------------------
  * Fused forward: Model.forward (collider) + ThermalNerfModel.get_outputs
  * [REF thermal_nerf_model.py:210-275]

@@ -109,6 +109,15 @@ class tn_closest_params(C.Structure):
     _fields_ = [("max_distance", C.c_double), ("reserved", C.c_int32 * 2)]
 
 
+class tn_project_camera(C.Structure):
+    _fields_ = [("c2w", C.c_float * 12), ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float)]
+
+
+class tn_project_params(C.Structure):
+    _fields_ = [("t_lo", C.c_double), ("t_hi", C.c_double), ("min_cos", C.c_double), ("near", C.c_double), ("width", C.c_int32),
+                ("height", C.c_int32), ("two_sided", C.c_int32), ("reserved", C.c_int32)]
+
+
 class tn_mesh_params(C.Structure):
     _fields_ = [("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("w2c", C.c_float * 12),
                 ("truncation", C.c_float), ("inv_truncation", C.c_float), ("min_accumulation", C.c_float), ("lo", C.c_float * 3),
@@ -278,6 +287,8 @@ SIGNATURES = {
     "tn_mesh_bvh_build": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _vp, _sz, _vp, _sz, _vp]),
     "tn_mesh_raycast": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i64, _vp, _sz, _vp, _vp, _vp, _i64, C.POINTER(tn_raycast_params)] + [_vp] * 9),
     "tn_mesh_closest": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i64, _vp, _sz, _vp, _vp, _i64, C.POINTER(tn_closest_params)] + [_vp] * 10),
+    "tn_mesh_project": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _vp, _sz, _vp, _vp, _vp, _i64, _vp, _vp, _i64, C.POINTER(tn_project_params)]
+                        + [_vp] * 8),
     "tn_mesh_tile": (_i32, []),
     "tn_mesh_scan_width": (_i32, []),
     "tn_mesh_workspace_bytes": (_sz, [_i32, _i32, _i32]),

@@ -1,7 +1,7 @@
 // The blob of tn_mesh_bvh_build as its readers see it (include/thermonerf_hip.h "THE BLOB"), the one place for it: the header and
 // the node, the constants of the tree and of the per-lane traversal stack, and what "usable face" means — the checked corners of a
 // face, its box in the numbers' order.  tn_mesh_bvh.hip builds the tree and casts rays through it, tn_mesh_closest.hip walks it for the
-// nearest face.
+// nearest face, tn_mesh_project.hip casts the occlusion rays of a projection: the slab and the face test are here for the two that cast.
 #pragma once
 #include "tn_device.h"
 
@@ -72,6 +72,60 @@ __device__ __forceinline__ void cross3(const double *a, const double *b, double 
     c[0] = __dsub_rn(__dmul_rn(a[1], b[2]), __dmul_rn(a[2], b[1]));
     c[1] = __dsub_rn(__dmul_rn(a[2], b[0]), __dmul_rn(a[0], b[2]));
     c[2] = __dsub_rn(__dmul_rn(a[0], b[1]), __dmul_rn(a[1], b[0]));
+}
+
+// ---- the ray against a box and against a face: the one definition of both readers that cast (tn_mesh_bvh.hip, tn_mesh_project.hip) ----
+
+constexpr double kSlack = 0x1.ffffffffp-1;  // 1 - 2^-32
+
+struct Ray {
+    double o[3], d[3], inv[3];
+    double t_min, t_end;
+};
+
+// the slab of the ray against a box: s = enter shrunk by 2^-32, the exit; true: the box PASSES
+__device__ __forceinline__ bool slab(const Ray &r, const float *lo, const float *hi, double &s, double &exit) {
+    double enter = r.t_min;
+    exit = r.t_end;
+    bool ok = true;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const double l = (double)lo[k], h = (double)hi[k];
+        if (r.d[k] == 0.0) {
+            ok = ok && l <= r.o[k] && r.o[k] <= h;
+        } else {
+            const double a = __dmul_rn(__dsub_rn(l, r.o[k]), r.inv[k]), b = __dmul_rn(__dsub_rn(h, r.o[k]), r.inv[k]);
+            enter = fmax(enter, fmin(a, b));
+            exit = fmin(exit, fmax(a, b));
+        }
+    }
+    s = __dmul_rn(enter, kSlack);
+    return ok && s <= exit;
+}
+
+// Moeller-Trumbore in fp64 and the face's own box; true: a HIT
+__device__ __forceinline__ bool face_hit(const Ray &r, const float *__restrict__ positions, const long long *i, int cull, double &t,
+                                         double &u, double &v) {
+    double p0[3], e1[3], e2[3], tv[3], pv[3], qv[3];
+    float lo[3], hi[3];
+    if (!face_box(positions, i, lo, hi)) return false;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        p0[k] = (double)positions[3 * i[0] + k];
+        e1[k] = __dsub_rn((double)positions[3 * i[1] + k], p0[k]);
+        e2[k] = __dsub_rn((double)positions[3 * i[2] + k], p0[k]);
+        tv[k] = __dsub_rn(r.o[k], p0[k]);
+    }
+    cross3(r.d, e2, pv);
+    const double det = dot3(e1, pv);
+    if (det == 0.0 || (cull == 1 && det < 0.0)) return false;
+    u = __ddiv_rn(dot3(tv, pv), det);
+    cross3(tv, e1, qv);
+    v = __ddiv_rn(dot3(r.d, qv), det);
+    t = __ddiv_rn(dot3(e2, qv), det);
+    if (!(u >= 0.0 && v >= 0.0 && __dadd_rn(u, v) <= 1.0 && r.t_min <= t && t <= r.t_end)) return false;
+    double s, exit;
+    return slab(r, lo, hi, s, exit) && s <= t;
 }
 
 __device__ __forceinline__ float quiet_nan() { return __int_as_float(0x7fc00000); }
