@@ -552,6 +552,15 @@ __device__ __forceinline__ unsigned f2key(float f) {
 __device__ __forceinline__ float key2f(unsigned k) {
     return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
 }
+// what the mesh sources share on top of the keys: the numbers' order with -0.0 below +0.0, "finite", the NaN and the colour they write
+__device__ __forceinline__ float min_ord(float a, float b) { return f2key(b) < f2key(a) ? b : a; }  // -0.0 below +0.0
+__device__ __forceinline__ float max_ord(float a, float b) { return f2key(b) > f2key(a) ? b : a; }
+__device__ __forceinline__ bool finite(float x) { return fabsf(x) <= 3.4028234663852886e38f; }  // (a NaN fails)
+__device__ __forceinline__ float quiet_nan() { return __int_as_float(0x7fc00000); }
+__device__ __forceinline__ uint8_t colour_of(double c) {
+    const double r = floor(__dadd_rn(c, 0.5));
+    return (uint8_t)(r < 0.0 ? 0.0 : (r > 255.0 ? 255.0 : r));
+}
 // Which [min, max] key pair a ray of a call belongs to.  DepthRenderer("expected") clips to the bounds of its CALL, which in the
 // reference is one eval_num_rays_per_chunk chunk of the frame; a launch that covers several such chunks (or parts of them:
 // tn_field_render_chunked_fwd) keeps one pair per chunk: chunk = (first_ray + ray) / chunk_rays, slot 0 = the call's first chunk.
@@ -684,6 +693,8 @@ namespace tn {  // host side: the entry points' argument checks and grid sizes (
 inline bool misaligned(const void *p, uintptr_t a) { return reinterpret_cast<uintptr_t>(p) % a != 0; }
 inline long long ceil_div(long long n, long long d) { return (n + d - 1) / d; }
 inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
+// the vertex and face counts every mesh entry refuses: 3 T must fit an int
+inline bool bad_counts(int64_t v, int64_t t) { return v < 0 || v > 0x7fffffffLL || t < 0 || 3 * t > 0x7fffffffLL; }
 constexpr long long kCUs = 256;  // compute units of the chip: a grid-stride kernel's cap is kCUs x its resident blocks per CU
 // blocks of a grid-stride launch: one per `units_per_block` units of work, at least one, at most `max_blocks`
 inline unsigned tn_grid_blocks(long long units, long long units_per_block, long long max_blocks) {

@@ -8,8 +8,9 @@
 //   4. sort         tn_sort_pairs over 31 bits: the faces in leaf order, straight into the blob
 //   5. nodes        one thread per internal node: Karras's radix tree, ties broken by the position in the sorted list
 //   6. fit          kDepthBound launches: a node whose children were done BEFORE this launch takes their boxes and is done
-// tn_mesh_raycast: a memset of the counts, the traversal (blocks of one wave, the stack of 64 entries per ray in LDS), one block that
-// finishes the statistics.  No allocation, no host synchronisation, no float atomics, no block ever waits for another; the integer
+// tn_mesh_raycast: a memset of the counts, the traversal (blocks of one wave, the stack of 64 entries per ray in LDS: the walk is
+// tn_mesh_bvh.h's, this file gives it the slab against the best hit so far and the face test), one block that finishes the statistics
+// (tn_mesh_bvh.h's finish_one).  No allocation, no host synchronisation, no float atomics, no block ever waits for another; the integer
 // atomics (extent, counts) are sums, minima and maxima, which do not depend on the order in which they are taken.
 #include "tn_mesh_bvh.h"
 
@@ -18,8 +19,7 @@ using namespace tn;
 namespace {
 
 constexpr int kTile = 256;
-constexpr int kRays = 64;         // rays per traversal block: one wave
-constexpr int kFinish = 1024;     // threads of the finish block
+constexpr int kRays = kLanes;     // rays per traversal block: one wave
 constexpr unsigned long long kUnusableKey = 1ull << 30;
 
 // ---- build ------------------------------------------------------------------------------------------------------------------
@@ -213,13 +213,7 @@ bvh_raycast_kernel(Cast a) {
     __shared__ int stack[kStack][kRays];  // entry e of lane l: no two lanes of the wave share a bank
     const int lane = threadIdx.x;
     const long long ray = (long long)blockIdx.x * kRays + lane;
-    const Header *header = reinterpret_cast<const Header *>(a.bvh);
-    const long long T = a.num_triangles;
-    const bool tree = T > 0 && a.num_vertices > 0 && header->magic == kMagic && header->version == kVersion && header->num_faces == (int)T;
-    long long num_nodes = tree ? header->num_nodes : 0;
-    num_nodes = num_nodes < T - 1 ? num_nodes : T - 1;
-    const int *faces = reinterpret_cast<const int *>(a.bvh + sizeof(Header));
-    const Node *nodes = reinterpret_cast<const Node *>(a.bvh + sizeof(Header) + ((size_t)T * sizeof(int) + 63) / 64 * 64);
+    const Tree tree = open_tree(a.bvh, a.num_triangles, a.num_vertices);
 
     Ray r;
     bool usable = ray < a.num_rays;
@@ -240,45 +234,19 @@ bvh_raycast_kernel(Cast a) {
     }
     int best_face = -1;
     double best_t = INFINITY, best_u = 0.0, best_v = 0.0;
-    bool overflow = false;
-    int cur = usable && tree ? header->root : kNone;
-    int sp = 0;
-    long long steps = 2 * T + 2;  // a tree visits each of its 2U - 1 nodes at most once: a foreign blob with a cycle ends here
-    while (cur != kNone && steps-- > 0) {
-        int next = kNone;
-        if (cur < 0) {
-            const long long leaf = ~cur;
-            const long long t = leaf < T ? faces[leaf] : -1;
-            long long i[3];
+    const bool overflow = walk(
+        tree, a.triangles, a.num_vertices, &stack[0][lane], usable,
+        [&](const float *lo, const float *hi, double &s) {
+            double unused;
+            return slab(r, lo, hi, s, unused) && s <= best_t;
+        },
+        [&](long long t, const long long *i) {
             double ft, fu, fv;
-            if (t >= 0 && t < T && corners(a.triangles, t, a.num_vertices, i) && face_hit(r, a.positions, i, a.cull, ft, fu, fv) &&
-                (ft < best_t || (ft == best_t && (int)t < best_face) || best_face < 0)) {
-                best_face = (int)t, best_t = ft, best_u = fu, best_v = fv;
-                if (a.any) break;
-            }
-        } else if (cur < num_nodes) {
-            const float4 *q = reinterpret_cast<const float4 *>(nodes + cur);
-            const float4 q0 = q[0], q1 = q[1], q2 = q[2], q3 = q[3];
-            const float lo0[3] = {q0.x, q0.y, q0.z}, lo1[3] = {q0.w, q1.x, q1.y};
-            const float hi0[3] = {q1.z, q1.w, q2.x}, hi1[3] = {q2.y, q2.z, q2.w};
-            const int c0 = __float_as_int(q3.x), c1 = __float_as_int(q3.y);
-            double s0, s1, unused;
-            const bool go0 = slab(r, lo0, hi0, s0, unused) && s0 <= best_t;
-            const bool go1 = slab(r, lo1, hi1, s1, unused) && s1 <= best_t;
-            if (go0 && go1) {
-                const bool swap = s1 < s0;  // the nearer child first
-                next = swap ? c1 : c0;
-                if (sp < kStack) stack[sp++][lane] = swap ? c0 : c1;
-                else overflow = true;  // that subtree is not descended
-            } else if (go0 || go1) {
-                next = go0 ? c0 : c1;
-            }
-        }
-        if (next == kNone && sp > 0) {
-            next = stack[--sp][lane];
-        }
-        cur = next;
-    }
+            if (!(face_hit(r, a.positions, i, a.cull, ft, fu, fv) && (ft < best_t || (ft == best_t && (int)t < best_face) || best_face < 0)))
+                return false;
+            best_face = (int)t, best_t = ft, best_u = fu, best_v = fv;
+            return a.any != 0;  // any-hit stops at its first
+        });
     const bool hit = best_face >= 0;
     if (ray < a.num_rays) {
         if (a.any) {
@@ -286,19 +254,8 @@ bvh_raycast_kernel(Cast a) {
         } else {
             float temp = quiet_nan();
             uint8_t rgb[3] = {0, 0, 0};
-            if (hit && (a.hit_temperature || a.hit_colors)) {
-                long long i[3];
-                corners(a.triangles, best_face, a.num_vertices, i);
-                const double w = __dsub_rn(__dsub_rn(1.0, best_u), best_v);
-                temp = (float)__dadd_rn(__dadd_rn(__dmul_rn(w, (double)a.temperature[i[0]]), __dmul_rn(best_u, (double)a.temperature[i[1]])),
-                                        __dmul_rn(best_v, (double)a.temperature[i[2]]));
-                if (a.hit_colors) {
-#pragma unroll
-                    for (int c = 0; c < 3; ++c)
-                        rgb[c] = colour_of(__dadd_rn(__dadd_rn(__dmul_rn(w, (double)a.colors[3 * i[0] + c]), __dmul_rn(best_u, (double)a.colors[3 * i[1] + c])),
-                                                     __dmul_rn(best_v, (double)a.colors[3 * i[2] + c])));
-                }
-            }
+            if (hit && (a.hit_temperature || a.hit_colors))
+                temp = surface_values(a.temperature, a.colors, a.triangles, a.num_vertices, best_face, best_u, best_v, a.hit_colors != nullptr, rgb);
             if (a.hit_face) a.hit_face[ray] = best_face;
             if (a.hit_t) a.hit_t[ray] = hit ? (float)best_t : quiet_nan();
             if (a.hit_uv) a.hit_uv[2 * ray] = hit ? (float)best_u : quiet_nan(), a.hit_uv[2 * ray + 1] = hit ? (float)best_v : quiet_nan();
@@ -315,62 +272,22 @@ bvh_raycast_kernel(Cast a) {
             if (hits) atomicAdd(a.counts + 0, (unsigned long long)__popcll(hits));
             if (good) atomicAdd(a.counts + 1, (unsigned long long)__popcll(good));
             if (over) atomicAdd(a.counts + 3, (unsigned long long)__popcll(over));
-            if (blockIdx.x == 0) a.counts[2] = tree ? (unsigned long long)(header->num_usable < 0 ? 0 : header->num_usable) : 0ull;
+            if (blockIdx.x == 0) a.counts[2] = (unsigned long long)tree.num_usable;
         }
     }
 }
 
-// counts[2] of a call without a ray
-__global__ void bvh_usable_kernel(const char *__restrict__ bvh, long long num_triangles, long long num_vertices, unsigned long long *counts) {
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    const Header *header = reinterpret_cast<const Header *>(bvh);
-    const bool tree = num_triangles > 0 && num_vertices > 0 && header->magic == kMagic && header->version == kVersion &&
-                      header->num_faces == (int)num_triangles;
-    counts[2] = tree && header->num_usable > 0 ? (unsigned long long)header->num_usable : 0ull;
-}
-
-// one block: SUM2 of (double)hit_temperature in ray order (a miss, the NaN, counts +0.0), the extremes over the hits
+// one block: SUM2 of (double)hit_temperature in ray order (a miss, the NaN, counts +0.0), the extremes over the hits.  finish_one
+// sums in the order this kernel always had — each run of 256 rays in order, then the runs in order —, here without the squares.
 __global__ void __launch_bounds__(kFinish)
 bvh_finish_kernel(const float *__restrict__ hit_temperature, long long num_rays, double *__restrict__ stats) {
-    __shared__ double partial[kFinish];
+    __shared__ double partial[kFinish], four[4];
     __shared__ unsigned all_min[kFinish], all_max[kFinish];
-    const long long blocks = (num_rays + 255) / 256;
-    double sum = 0.0;
-    unsigned kmin = ~0u, kmax = 0u;
-    for (long long first = 0; first < blocks; first += kFinish) {
-        const long long b = first + threadIdx.x;
-        double own = 0.0;
-        if (b < blocks) {
-            const long long end = (b + 1) * 256 < num_rays ? (b + 1) * 256 : num_rays;
-            for (long long k = b * 256; k < end; ++k) {
-                const float x = hit_temperature[k];
-                const bool hit = x == x;
-                own = __dadd_rn(own, hit ? (double)x : 0.0);
-                kmin = hit ? min(kmin, f2key(x)) : kmin, kmax = hit ? max(kmax, f2key(x)) : kmax;
-            }
-        }
-        partial[threadIdx.x] = own;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            const long long here = blocks - first < kFinish ? blocks - first : kFinish;
-            for (int k = 0; k < here; ++k) sum = __dadd_rn(sum, partial[k]);
-        }
-        __syncthreads();
-    }
-    all_min[threadIdx.x] = kmin, all_max[threadIdx.x] = kmax;
-    __syncthreads();
-    if (threadIdx.x != 0) return;
-    for (int k = 1; k < kFinish; ++k) kmin = min(kmin, all_min[k]), kmax = max(kmax, all_max[k]);
-    stats[0] = sum;
-    stats[1] = kmin <= kmax ? (double)key2f(kmin) : (double)INFINITY;
-    stats[2] = kmin <= kmax ? (double)key2f(kmax) : -(double)INFINITY;
+    finish_one<false>(hit_temperature, num_rays, partial, nullptr, all_min, all_max, four);
+    if (threadIdx.x == 0) stats[0] = four[0], stats[1] = four[2], stats[2] = four[3];
 }
 
-inline bool bad_counts(int64_t v, int64_t t) { return v < 0 || v > 0x7fffffffLL || t < 0 || 3 * t > 0x7fffffffLL; }
-
 inline long long tiles_of(long long n) { return ceil_div(n, kTile); }
-
-inline size_t faces_bytes(long long t) { return align_up((size_t)t * sizeof(int), 64); }
 
 inline size_t blob_bytes(long long t) { return sizeof(Header) + faces_bytes(t) + (size_t)(t > 1 ? t - 1 : 0) * sizeof(Node); }
 
@@ -503,7 +420,7 @@ int tn_mesh_raycast(const float *positions, const float *temperature, const uint
     if (!any && counts) {
         if (hipMemsetAsync(counts, 0, 4 * sizeof(int64_t), s) != hipSuccess) return TN_ERR_LAUNCH;
         if (num_rays == 0) {
-            hipLaunchKernelGGL(bvh_usable_kernel, dim3(1), dim3(TN_WAVE), 0, s, a.bvh, a.num_triangles, a.num_vertices, a.counts);
+            hipLaunchKernelGGL(tree_usable_kernel, dim3(1), dim3(TN_WAVE), 0, s, a.bvh, a.num_triangles, a.num_vertices, a.counts);
             TN_LAUNCH_CHECK();
         }
     }

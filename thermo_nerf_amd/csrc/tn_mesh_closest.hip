@@ -1,10 +1,10 @@
 // The nearest point of an indexed triangle list to every query point (DESIGN.md "Closest point"; include/thermonerf_hip.h defines
 // every output to the bit, without reference to the tree): the second reader of tn_mesh_bvh_build's blob.
-// tn_mesh_closest, launches on the caller's stream: a memset of the counts; the walk — blocks of one wave, one point per lane, a node
-// is one 64-byte fetch that gives both children's bound b (the squared distance from the point to the box), a child whose b exceeds
-// the best d2 so far is skipped, the child with the smaller b is descended first and the other pushed on a stack of 64 entries per
-// lane in LDS; a popped entry is tested again, against the best as it is by then: an internal node through its children's bounds,
-// a leaf through the bound of its face's own box before any of the face's arithmetic —; one block that finishes the statistics.
+// tn_mesh_closest, launches on the caller's stream: a memset of the counts; the walk — blocks of one wave, one point per lane; the
+// loop itself is tn_mesh_bvh.h's walk, and this file gives it its two tests: a child's bound b (the squared distance from the point
+// to the box) orders the children and a child whose b exceeds the best d2 so far is skipped, also when it is popped later, against
+// the best as it is by then; a leaf goes through the bound of its face's own box before any of the face's arithmetic —; one block
+// that finishes the statistics (tn_mesh_bvh.h's finish_one).
 // No allocation, no host synchronisation, no float atomics, no block ever waits for another; the integer atomics are sums of the
 // waves' ballots.
 #include "tn_mesh_bvh.h"
@@ -13,8 +13,7 @@ using namespace tn;
 
 namespace {
 
-constexpr int kPoints = 64;    // points per block: one wave
-constexpr int kFinish = 1024;  // threads of the finish block
+constexpr int kPoints = kLanes;  // points per block: one wave
 
 // b of a box against the point: per axis the gap max(lo - q, q - hi, 0), then the squared length in the order of d2
 __device__ __forceinline__ double box_bound(const double *q, const float *lo, const float *hi) {
@@ -118,13 +117,7 @@ bvh_closest_kernel(Query a) {
     __shared__ int stack[kStack][kPoints];      // entry e of lane l: no two lanes of the wave share a bank
     const int lane = threadIdx.x;
     const long long point = (long long)blockIdx.x * kPoints + lane;
-    const Header *header = reinterpret_cast<const Header *>(a.bvh);
-    const long long T = a.num_triangles;
-    const bool tree = T > 0 && a.num_vertices > 0 && header->magic == kMagic && header->version == kVersion && header->num_faces == (int)T;
-    long long num_nodes = tree ? header->num_nodes : 0;
-    num_nodes = num_nodes < T - 1 ? num_nodes : T - 1;
-    const int *faces = reinterpret_cast<const int *>(a.bvh + sizeof(Header));
-    const Node *nodes = reinterpret_cast<const Node *>(a.bvh + sizeof(Header) + ((size_t)T * sizeof(int) + 63) / 64 * 64);
+    const Tree tree = open_tree(a.bvh, a.num_triangles, a.num_vertices);
 
     double q[3] = {0.0, 0.0, 0.0};
     bool usable = point < a.num_points;
@@ -139,58 +132,26 @@ bvh_closest_kernel(Query a) {
     int best_face = -1;
     Nearest best;
     best.d2 = a.r2, best.u = best.v = 0.0, best.c[0] = best.c[1] = best.c[2] = 0.0;  // d2: the cut until a face is found, then the winner's
-    bool overflow = false;
-    int cur = usable && tree ? header->root : kNone;
-    int sp = 0;
-    long long steps = 2 * T + 2;  // a tree visits each of its 2U - 1 nodes at most once: a foreign blob with a cycle ends here
-    auto pop = [&]() { return sp > 0 ? stack[--sp][lane] : kNone; };
-    while (cur != kNone && steps-- > 0) {
-        int next = kNone;
-        if (cur < 0) {
-            const long long leaf = ~cur;
-            const long long t = leaf < T ? faces[leaf] : -1;
-            long long i[3];
+    const bool overflow = walk(
+        tree, a.triangles, a.num_vertices, &stack[0][lane], usable,
+        [&](const float *lo, const float *hi, double &b) {
+            b = box_bound(q, lo, hi);
+            return !(b > best.d2);  // skipped only when strictly beyond the best, or the cut
+        },
+        [&](long long t, const long long *i) {
             Nearest own;
-            if (t >= 0 && t < T && corners(a.triangles, t, a.num_vertices, i) && face_nearest(q, a.positions, i, best.d2, own) &&
+            if (face_nearest(q, a.positions, i, best.d2, own) &&
                 (own.d2 < best.d2 || (own.d2 == best.d2 && (best_face < 0 || (int)t < best_face)))) {
                 best = own, best_face = (int)t;
             }
-        } else if (cur < num_nodes) {
-            const float4 *f = reinterpret_cast<const float4 *>(nodes + cur);
-            const float4 q0 = f[0], q1 = f[1], q2 = f[2], q3 = f[3];
-            const float lo0[3] = {q0.x, q0.y, q0.z}, lo1[3] = {q0.w, q1.x, q1.y};
-            const float hi0[3] = {q1.z, q1.w, q2.x}, hi1[3] = {q2.y, q2.z, q2.w};
-            const int c0 = __float_as_int(q3.x), c1 = __float_as_int(q3.y);
-            const double b0 = box_bound(q, lo0, hi0), b1 = box_bound(q, lo1, hi1);
-            const bool go0 = !(b0 > best.d2), go1 = !(b1 > best.d2);  // skipped only when strictly beyond the best, or the cut
-            if (go0 && go1) {
-                const bool swap = b1 < b0;  // the nearer child first
-                next = swap ? c1 : c0;
-                if (sp < kStack) stack[sp++][lane] = swap ? c0 : c1;
-                else overflow = true;  // that subtree is not descended
-            } else if (go0 || go1) {
-                next = go0 ? c0 : c1;
-            }
-        }
-        cur = next == kNone ? pop() : next;
-    }
+            return false;
+        });
     const bool found = best_face >= 0;
     if (point < a.num_points) {
         float temp = quiet_nan();
         uint8_t rgb[3] = {0, 0, 0};
-        if (found && (a.closest_temperature || a.closest_colors || a.difference)) {
-            long long i[3];
-            corners(a.triangles, best_face, a.num_vertices, i);
-            const double w = __dsub_rn(__dsub_rn(1.0, best.u), best.v);
-            temp = (float)__dadd_rn(__dadd_rn(__dmul_rn(w, (double)a.temperature[i[0]]), __dmul_rn(best.u, (double)a.temperature[i[1]])),
-                                    __dmul_rn(best.v, (double)a.temperature[i[2]]));
-            if (a.closest_colors) {
-#pragma unroll
-                for (int c = 0; c < 3; ++c)
-                    rgb[c] = colour_of(__dadd_rn(__dadd_rn(__dmul_rn(w, (double)a.colors[3 * i[0] + c]), __dmul_rn(best.u, (double)a.colors[3 * i[1] + c])),
-                                                 __dmul_rn(best.v, (double)a.colors[3 * i[2] + c])));
-            }
-        }
+        if (found && (a.closest_temperature || a.closest_colors || a.difference))
+            temp = surface_values(a.temperature, a.colors, a.triangles, a.num_vertices, best_face, best.u, best.v, a.closest_colors != nullptr, rgb);
         if (a.closest_face) a.closest_face[point] = best_face;
         if (a.closest_distance) a.closest_distance[point] = found ? (float)__dsqrt_rn(best.d2) : quiet_nan();
         if (a.closest_point) {
@@ -214,57 +175,9 @@ bvh_closest_kernel(Query a) {
             if (with) atomicAdd(a.counts + 0, (unsigned long long)__popcll(with));
             if (good) atomicAdd(a.counts + 1, (unsigned long long)__popcll(good));
             if (over) atomicAdd(a.counts + 3, (unsigned long long)__popcll(over));
-            if (blockIdx.x == 0) a.counts[2] = tree ? (unsigned long long)(header->num_usable < 0 ? 0 : header->num_usable) : 0ull;
+            if (blockIdx.x == 0) a.counts[2] = (unsigned long long)tree.num_usable;
         }
     }
-}
-
-// counts[2] of a call without a point
-__global__ void closest_usable_kernel(const char *__restrict__ bvh, long long num_triangles, long long num_vertices, unsigned long long *counts) {
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    const Header *header = reinterpret_cast<const Header *>(bvh);
-    const bool tree = num_triangles > 0 && num_vertices > 0 && header->magic == kMagic && header->version == kVersion &&
-                      header->num_faces == (int)num_triangles;
-    counts[2] = tree && header->num_usable > 0 ? (unsigned long long)header->num_usable : 0ull;
-}
-
-// SUM2 of (double)values and of their squares in point order (the NaN of a point without the value counts +0.0), the extremes over
-// the points that have it, into out[0 .. 3]; values == nullptr: no point has the value.  Every thread of the one block calls it.
-__device__ void finish_one(const float *__restrict__ values, long long n, double *partial, double *partial2, unsigned *all_min, unsigned *all_max,
-                           double *__restrict__ out) {
-    const long long blocks = values ? (n + 255) / 256 : 0;
-    double sum = 0.0, sum2 = 0.0;
-    unsigned kmin = ~0u, kmax = 0u;
-    for (long long first = 0; first < blocks; first += kFinish) {
-        const long long b = first + threadIdx.x;
-        double own = 0.0, own2 = 0.0;
-        if (b < blocks) {
-            const long long end = (b + 1) * 256 < n ? (b + 1) * 256 : n;
-            for (long long k = b * 256; k < end; ++k) {
-                const float x = values[k];
-                const bool has = x == x;
-                const double d = has ? (double)x : 0.0;
-                own = __dadd_rn(own, d), own2 = __dadd_rn(own2, __dmul_rn(d, d));
-                kmin = has ? min(kmin, f2key(x)) : kmin, kmax = has ? max(kmax, f2key(x)) : kmax;
-            }
-        }
-        partial[threadIdx.x] = own, partial2[threadIdx.x] = own2;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            const long long here = blocks - first < kFinish ? blocks - first : kFinish;
-            for (int k = 0; k < here; ++k) sum = __dadd_rn(sum, partial[k]), sum2 = __dadd_rn(sum2, partial2[k]);
-        }
-        __syncthreads();
-    }
-    all_min[threadIdx.x] = kmin, all_max[threadIdx.x] = kmax;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int k = 1; k < kFinish; ++k) kmin = min(kmin, all_min[k]), kmax = max(kmax, all_max[k]);
-        out[0] = sum, out[1] = sum2;
-        out[2] = kmin <= kmax ? (double)key2f(kmin) : (double)INFINITY;
-        out[3] = kmin <= kmax ? (double)key2f(kmax) : -(double)INFINITY;
-    }
-    __syncthreads();
 }
 
 __global__ void __launch_bounds__(kFinish)
@@ -275,8 +188,6 @@ closest_finish_kernel(const float *__restrict__ closest_distance, const float *_
     finish_one(closest_distance, num_points, partial, partial2, all_min, all_max, stats);
     finish_one(difference, num_points, partial, partial2, all_min, all_max, stats + 4);
 }
-
-inline bool bad_counts(int64_t v, int64_t t) { return v < 0 || v > 0x7fffffffLL || t < 0 || 3 * t > 0x7fffffffLL; }
 
 }  // namespace
 
@@ -315,7 +226,7 @@ int tn_mesh_closest(const float *positions, const float *temperature, const uint
     if (counts) {
         if (hipMemsetAsync(counts, 0, 4 * sizeof(int64_t), s) != hipSuccess) return TN_ERR_LAUNCH;
         if (num_points == 0) {
-            hipLaunchKernelGGL(closest_usable_kernel, dim3(1), dim3(TN_WAVE), 0, s, a.bvh, a.num_triangles, a.num_vertices, a.counts);
+            hipLaunchKernelGGL(tree_usable_kernel, dim3(1), dim3(TN_WAVE), 0, s, a.bvh, a.num_triangles, a.num_vertices, a.counts);
             TN_LAUNCH_CHECK();
         }
     }

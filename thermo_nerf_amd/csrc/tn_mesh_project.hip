@@ -3,9 +3,9 @@
 // tn_mesh_project, launches on the caller's stream: a memset of the counts; the projection — blocks of one wave, one point per lane,
 // the loop over the cameras INSIDE the thread with the point's sums in registers, so that the order of every sum is the cameras'
 // order whatever the schedule; the camera's record is indexed by the loop counter alone and is read once per wave; the cheap clauses
-// (behind, outside the image, facing) come before the walk, which is the ray cast's any-hit traversal (tn_mesh_bvh.h holds the slab
-// and the face test of both): a node is one 64-byte fetch, the nearer child first, the other on a stack of 64 entries per lane in
-// LDS —; one block that finishes the statistics.
+// (behind, outside the image, facing) come before the walk, which is tn_mesh_bvh.h's walk under the slab alone, stopped by the first
+// face_hit: the ray cast's any-hit traversal (tn_mesh_bvh.h holds the slab and the face test of both) —; one block that finishes the
+// statistics (tn_mesh_bvh.h's finish_one).
 // No allocation, no host synchronisation, no float atomics, no block ever waits for another; the integer atomics are sums of the
 // waves' counts.
 #include "tn_mesh_bvh.h"
@@ -14,10 +14,10 @@ using namespace tn;
 
 namespace {
 
-constexpr int kPoints = 64;    // points per block: one wave, as tn_mesh_bvh.hip's kRays (16 KiB of stack: ten blocks share a CU's LDS)
-constexpr int kFinish = 1024;  // threads of the finish block
+constexpr int kPoints = kLanes;  // points per block: one wave, as tn_mesh_bvh.hip's kRays (16 KiB of stack: ten blocks share a CU's LDS)
 constexpr int kMaxSide = 16384;
-constexpr double kVisibleFraction = 0x1.ffcp-1;  // 1 - 2^-10: where visible_from stops its rays
+constexpr double kVisibleFraction = 0x1.ff8p-1;  // 1 - 2^-10: where visible_from stops its rays
+static_assert(kVisibleFraction == 1.0 - 1.0 / 1024.0, "include/thermonerf_hip.h, clause 5");
 
 struct Camera {  // tn_project_camera
     float c2w[12];
@@ -61,14 +61,7 @@ bvh_project_kernel(Project a) {
     __shared__ int stack[kStack][kPoints];  // entry e of lane l: no two lanes of the wave share a bank
     const int lane = threadIdx.x;
     const long long point = (long long)blockIdx.x * kPoints + lane;
-    const Header *header = reinterpret_cast<const Header *>(a.bvh);
-    const long long T = a.num_triangles;
-    const bool tree = T > 0 && a.num_vertices > 0 && header->magic == kMagic && header->version == kVersion && header->num_faces == (int)T;
-    long long num_nodes = tree ? header->num_nodes : 0;
-    num_nodes = num_nodes < T - 1 ? num_nodes : T - 1;
-    const int root = tree ? header->root : kNone;
-    const int *faces = reinterpret_cast<const int *>(a.bvh + sizeof(Header));
-    const Node *nodes = reinterpret_cast<const Node *>(a.bvh + sizeof(Header) + ((size_t)T * sizeof(int) + 63) / 64 * 64);
+    const Tree tree = open_tree(a.bvh, a.num_triangles, a.num_vertices);
     const int W = a.width, H = a.height;
 
     float p[3] = {0.0f, 0.0f, 0.0f};
@@ -136,42 +129,16 @@ bvh_project_kernel(Project a) {
 #pragma unroll
             for (int j = 0; j < 3; ++j) r.inv[j] = __ddiv_rn(1.0, r.d[j]);
             r.t_min = 0.0, r.t_end = kVisibleFraction;
-            bool overflow = false;
-            int cur = ray_ok ? root : kNone;
-            int sp = 0;
-            long long steps = 2 * T + 2;  // a tree visits each of its 2U - 1 nodes at most once: a foreign blob with a cycle ends here
-            while (cur != kNone && steps-- > 0) {
-                int next = kNone;
-                if (cur < 0) {
-                    const long long leaf = ~cur;
-                    const long long t = leaf < T ? faces[leaf] : -1;
-                    long long i[3];
+            const bool overflow = walk(
+                tree, a.triangles, a.num_vertices, &stack[0][lane], ray_ok,
+                [&](const float *lo, const float *hi, double &s) {
+                    double unused;
+                    return slab(r, lo, hi, s, unused);
+                },
+                [&](long long, const long long *i) {
                     double ft, fu, fv;
-                    if (t >= 0 && t < T && corners(a.triangles, t, a.num_vertices, i) && face_hit(r, a.positions, i, 0, ft, fu, fv)) {
-                        hit = true;
-                        break;
-                    }
-                } else if (cur < num_nodes) {
-                    const float4 *q = reinterpret_cast<const float4 *>(nodes + cur);
-                    const float4 q0 = q[0], q1 = q[1], q2 = q[2], q3 = q[3];
-                    const float lo0[3] = {q0.x, q0.y, q0.z}, lo1[3] = {q0.w, q1.x, q1.y};
-                    const float hi0[3] = {q1.z, q1.w, q2.x}, hi1[3] = {q2.y, q2.z, q2.w};
-                    const int c0 = __float_as_int(q3.x), c1 = __float_as_int(q3.y);
-                    double s0, s1, unused;
-                    const bool go0 = slab(r, lo0, hi0, s0, unused);
-                    const bool go1 = slab(r, lo1, hi1, s1, unused);
-                    if (go0 && go1) {
-                        const bool swap = s1 < s0;  // the nearer child first
-                        next = swap ? c1 : c0;
-                        if (sp < kStack) stack[sp++][lane] = swap ? c0 : c1;
-                        else overflow = true;  // that subtree is not descended
-                    } else if (go0 || go1) {
-                        next = go0 ? c0 : c1;
-                    }
-                }
-                if (next == kNone && sp > 0) next = stack[--sp][lane];
-                cur = next;
-            }
+                    return hit = face_hit(r, a.positions, i, 0, ft, fu, fv);  // the first hit ends the walk
+                });
             if (overflow) ++over;
         }
         if (!go || hit) continue;
@@ -232,45 +199,6 @@ __global__ void project_cameras_kernel(const Camera *__restrict__ cameras, long 
     counts[2] = good;
 }
 
-// SUM2 of (double)values and of their squares in point order (the NaN of a point without the value counts +0.0), the extremes over
-// the points that have it, into out[0 .. 3]; values == nullptr: no point has the value.  Every thread of the one block calls it.
-__device__ void finish_one(const float *__restrict__ values, long long n, double *partial, double *partial2, unsigned *all_min, unsigned *all_max,
-                           double *out) {
-    const long long blocks = values ? (n + 255) / 256 : 0;
-    double sum = 0.0, sum2 = 0.0;
-    unsigned kmin = ~0u, kmax = 0u;
-    for (long long first = 0; first < blocks; first += kFinish) {
-        const long long b = first + threadIdx.x;
-        double own = 0.0, own2 = 0.0;
-        if (b < blocks) {
-            const long long end = (b + 1) * 256 < n ? (b + 1) * 256 : n;
-            for (long long k = b * 256; k < end; ++k) {
-                const float x = values[k];
-                const bool has = x == x;
-                const double d = has ? (double)x : 0.0;
-                own = __dadd_rn(own, d), own2 = __dadd_rn(own2, __dmul_rn(d, d));
-                kmin = has ? min(kmin, f2key(x)) : kmin, kmax = has ? max(kmax, f2key(x)) : kmax;
-            }
-        }
-        partial[threadIdx.x] = own, partial2[threadIdx.x] = own2;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            const long long here = blocks - first < kFinish ? blocks - first : kFinish;
-            for (int k = 0; k < here; ++k) sum = __dadd_rn(sum, partial[k]), sum2 = __dadd_rn(sum2, partial2[k]);
-        }
-        __syncthreads();
-    }
-    all_min[threadIdx.x] = kmin, all_max[threadIdx.x] = kmax;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int k = 1; k < kFinish; ++k) kmin = min(kmin, all_min[k]), kmax = max(kmax, all_max[k]);
-        out[0] = sum, out[1] = sum2;
-        out[2] = kmin <= kmax ? (double)key2f(kmin) : (double)INFINITY;
-        out[3] = kmin <= kmax ? (double)key2f(kmax) : -(double)INFINITY;
-    }
-    __syncthreads();
-}
-
 __global__ void __launch_bounds__(kFinish)
 project_finish_kernel(const float *__restrict__ difference, const float *__restrict__ spread, const float *__restrict__ measured,
                       long long num_points, double *__restrict__ stats) {
@@ -283,8 +211,6 @@ project_finish_kernel(const float *__restrict__ difference, const float *__restr
     finish_one(measured, num_points, partial, partial2, all_min, all_max, four);
     if (threadIdx.x == 0) stats[6] = four[0], stats[7] = 0.0;
 }
-
-inline bool bad_counts(int64_t v, int64_t t) { return v < 0 || v > 0x7fffffffLL || t < 0 || 3 * t > 0x7fffffffLL; }
 
 inline bool is_finite(double x) { return x - x == 0.0; }
 

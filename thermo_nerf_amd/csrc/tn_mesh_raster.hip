@@ -54,7 +54,7 @@ struct alignas(8) Partial {  // of 256 pixels
     int covered, pad;
 };
 
-__device__ __forceinline__ bool finite(float x) { return fabsf(x) <= 3.4028234663852886e38f; }  // (a NaN fails)
+using tn::finite;  // (float), beside the double of this file
 __device__ __forceinline__ bool finite(double x) { return fabs(x) <= 1.7976931348623157e308; }
 
 __device__ __forceinline__ double along(const double *q, const double *a) {
@@ -251,13 +251,6 @@ raster_sweep_kernel(const int *__restrict__ large_list, const long long *__restr
     }
 }
 
-__device__ __forceinline__ float quiet_nan() { return __int_as_float(0x7fc00000); }
-
-__device__ __forceinline__ uint8_t colour_of(double c) {
-    const double r = floor(__dadd_rn(c, 0.5));
-    return (uint8_t)(r < 0.0 ? 0.0 : (r > 255.0 ? 255.0 : r));
-}
-
 __global__ void __launch_bounds__(kTile)
 raster_resolve_kernel(const unsigned long long *__restrict__ keys, long long num_pixels, int width, const Face *__restrict__ records,
                       long long num_triangles, long long num_vertices, const float *__restrict__ temperature,
@@ -364,7 +357,6 @@ __global__ void raster_empty_kernel(long long *__restrict__ counts, double *__re
     stats[2] = -(double)INFINITY;
 }
 
-inline bool bad_counts(int64_t v, int64_t t) { return v < 0 || v > 0x7fffffffLL || t < 0 || 3 * t > 0x7fffffffLL; }
 inline bool bad_side(int32_t n) { return n < 1 || n > kMaxSide; }
 inline bool host_finite(double x) { return x - x == 0.0; }
 

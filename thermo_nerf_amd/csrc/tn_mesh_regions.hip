@@ -80,8 +80,6 @@ __device__ __forceinline__ void acc_join(Acc &a, const Acc &r) {
     if (r.cold >= 0) colder(a.cold, a.tcold, r.cold, r.tcold);
 }
 
-__device__ __forceinline__ bool finite(float x) { return fabsf(x) <= 3.4028234663852886e38f; }  // (a NaN fails)
-
 constexpr int kUsable = 1, kSelected = 2;
 
 __global__ void __launch_bounds__(kTile)
@@ -310,8 +308,6 @@ block_sums_kernel(const unsigned long long *__restrict__ sorted, const int *__re
     partials[b] = a;
 }
 
-__device__ __forceinline__ float quiet_nan() { return __int_as_float(0x7fc00000); }
-
 __global__ void __launch_bounds__(kTile)
 regions_kernel(Regions g, long long num_vertices, const int *__restrict__ component_triangles, const long long *__restrict__ counts,
                const long long *__restrict__ num_blocks, long long max_blocks, const Acc *__restrict__ partials,
@@ -376,8 +372,6 @@ __global__ void totals_kernel(const long long *__restrict__ counts, long long nu
     for (long long b = 0; b < blocks; ++b) s = __dadd_rn(s, partials[y * blocks_per_list + b]);
     totals[y] = s;
 }
-
-inline bool bad_counts(int64_t v, int64_t t) { return v < 0 || v > 0x7fffffffLL || t < 0 || 3 * t > 0x7fffffffLL; }
 
 inline long long tiles_of(long long n) { return ceil_div(n, kTile); }
 

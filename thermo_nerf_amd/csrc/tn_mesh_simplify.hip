@@ -203,8 +203,6 @@ vertex_map_kernel(const int *__restrict__ rank, const int *__restrict__ cluster_
     vertex_map[i] = r >= 0 ? cluster_out[r] : -1;
 }
 
-inline bool bad_counts(int64_t v, int64_t t) { return v < 0 || v > 0x7fffffffLL || t < 0 || 3 * t > 0x7fffffffLL; }
-
 inline long long tiles_of(long long n) { return ceil_div(n, kTile); }
 
 inline size_t keys_bytes(long long n) { return (size_t)n * sizeof(unsigned long long); }

@@ -19,9 +19,8 @@ from torch import Tensor
 
 from .. import _hip
 from ._common import out_tensor
-from .components import MAX_COUNT
 from .mesh import ThermalMesh
-from .raycast import MeshBVH, _mesh_arrays
+from .raycast import MeshBVH, _fill_differences, _mesh_colors, _moments, _points, _tree_arrays
 
 
 def check_max_distance(max_distance: float) -> None:
@@ -43,17 +42,8 @@ def mesh_closest_into(bvh: MeshBVH, points: Tensor, *, max_distance: float = mat
     ``stats`` float64 [8] (ordered sum, ordered sum of squares, minimum, maximum of the distances, then of the differences; needs
     ``closest_distance``): each optional."""
     check_max_distance(float(max_distance))
-    mesh = bvh.mesh
-    p, t, tri, v, n = _mesh_arrays(mesh)
-    if v != bvh.num_vertices or n != bvh.num_triangles:
-        raise ValueError("the tree belongs to another mesh: its vertex and face counts differ")
-    dev = p.device
-    blob = bvh.blob
-    if not isinstance(blob, Tensor) or not blob.is_cuda or blob.device != dev or not blob.is_contiguous():
-        raise ValueError("the tree's blob must be a contiguous tensor on the mesh's device")
-    q = _hip.require_device_tensor(points, "points")
-    if q.dim() != 2 or q.shape[1] != 3 or 3 * q.shape[0] > MAX_COUNT:
-        raise ValueError("points must be [N, 3] with 3 N <= 2^31 - 1")
+    p, t, tri, v, n, dev, blob = _tree_arrays(bvh)
+    q = _points(points, "N")
     if q.device != dev:
         raise ValueError("the points must be on the mesh's device")
     count = int(q.shape[0])
@@ -61,13 +51,7 @@ def mesh_closest_into(bvh: MeshBVH, points: Tensor, *, max_distance: float = mat
         point_temperature = _hip.require_device_tensor(point_temperature, "point_temperature")
         if point_temperature.numel() != count or point_temperature.device != dev:
             raise ValueError("point_temperature must hold N values on the mesh's device")
-    colors = None
-    if closest_colors is not None:
-        colors = _hip.require_device_tensor(mesh.colors, "colors", torch.uint8)
-        if colors.numel() != 3 * v or colors.device != dev:
-            raise ValueError("colors must be [V, 3] on the mesh's device")
-        if v == 0:
-            colors = torch.zeros((1, 3), dtype=torch.uint8, device=dev)
+    colors = _mesh_colors(bvh.mesh, v, dev) if closest_colors is not None else None
     if difference is not None and (point_temperature is None or closest_temperature is None):
         raise ValueError("difference is point_temperature - closest_temperature: give both")
     if stats is not None and closest_distance is None:
@@ -119,10 +103,6 @@ class ClosestPoints:
     matched: int = 0                      # points with a difference that is a number
 
 
-def _moments(total: float, squares: float, count: int):
-    return (total / count, math.sqrt(squares / count)) if count else (math.nan, math.nan)
-
-
 @torch.no_grad()
 def mesh_closest(bvh: MeshBVH, points: Tensor, *, max_distance: float = math.inf, point_temperature: Optional[Tensor] = None
                  ) -> ClosestPoints:
@@ -131,10 +111,7 @@ def mesh_closest(bvh: MeshBVH, points: Tensor, *, max_distance: float = math.inf
     check_max_distance(float(max_distance))
     p = _hip.require_device_tensor(bvh.mesh.positions, "positions")
     dev = p.device
-    q = _hip.require_device_tensor(points, "points")
-    n = int(q.shape[0]) if q.dim() == 2 else -1
-    if n < 0:
-        raise ValueError("points must be [N, 3] with 3 N <= 2^31 - 1")
+    n = int(_points(points, "N", rows_only=True).shape[0])
     with torch.cuda.device(dev):
         head = torch.zeros((13,), dtype=torch.int64, device=dev)  # the four counts, the eight statistics, the matched points
         face = torch.empty((n,), dtype=torch.int32, device=dev)
@@ -154,9 +131,7 @@ def mesh_closest(bvh: MeshBVH, points: Tensor, *, max_distance: float = math.inf
     out = ClosestPoints(face, distance, where, uv, temperature, colors, difference, found, usable_points, usable_faces, limit, mean, rms,
                         s[2], s[3])
     if difference is not None:
-        out.matched = int(first[12])
-        out.mean_difference, out.rms_difference = _moments(s[4], s[5], out.matched)
-        out.min_difference, out.max_difference = s[6], s[7]
+        _fill_differences(out, int(first[12]), s[4:8])
     return out
 
 

@@ -20,9 +20,8 @@ from torch import Tensor
 
 from .. import _hip
 from ._common import out_tensor
-from .components import MAX_COUNT
 from .mesh import ThermalMesh
-from .raycast import CameraView, MeshBVH, _mesh_arrays, check_camera
+from .raycast import CameraView, MeshBVH, _fill_differences, _points, _tree_arrays, check_camera
 from .smooth import vertex_normals
 from .thermogram import MAX_SIDE
 
@@ -75,17 +74,8 @@ def project_images_into(bvh: MeshBVH, points: Tensor, normals: Optional[Tensor],
     sum, sum of squares, minimum, maximum of the differences; sum and maximum of the spreads; sum of the measurements; 0 — each from
     its output array): each optional."""
     lo, hi = check_projection(temperature_bounds, float(min_cos), float(near))
-    mesh = bvh.mesh
-    p, t, tri, v, n = _mesh_arrays(mesh)
-    if v != bvh.num_vertices or n != bvh.num_triangles:
-        raise ValueError("the tree belongs to another mesh: its vertex and face counts differ")
-    dev = p.device
-    blob = bvh.blob
-    if not isinstance(blob, Tensor) or not blob.is_cuda or blob.device != dev or not blob.is_contiguous():
-        raise ValueError("the tree's blob must be a contiguous tensor on the mesh's device")
-    q = _hip.require_device_tensor(points, "points")
-    if q.dim() != 2 or q.shape[1] != 3 or 3 * q.shape[0] > MAX_COUNT:
-        raise ValueError("points must be [P, 3] with 3 P <= 2^31 - 1")
+    p, t, tri, v, n, dev, blob = _tree_arrays(bvh)
+    q = _points(points, "P")
     count = int(q.shape[0])
     if normals is not None:
         normals = _hip.require_device_tensor(normals, "normals")
@@ -166,10 +156,7 @@ def project_images(bvh: MeshBVH, points: Tensor, normals: Optional[Tensor], came
     records, width, height = camera_records(cameras)
     p = _hip.require_device_tensor(bvh.mesh.positions, "positions")
     dev = p.device
-    q = _hip.require_device_tensor(points, "points")
-    n = int(q.shape[0]) if q.dim() == 2 else -1
-    if n < 0:
-        raise ValueError("points must be [P, 3] with 3 P <= 2^31 - 1")
+    n = int(_points(points, "P", rows_only=True).shape[0])
     photos = _hip.require_device_tensor(images, "images", torch.uint8)
     if photos.dim() != 3 or photos.shape[0] != len(records) or (len(records) and tuple(photos.shape[1:]) != (height, width)):
         raise ValueError(f"images must be uint8 [K, H, W] = [{len(records)}, {height}, {width}] like the views, got {tuple(photos.shape)}")
@@ -191,10 +178,7 @@ def project_images(bvh: MeshBVH, points: Tensor, normals: Optional[Tensor], came
                                 seen / n if n else 0.0, accepted / n if n else 0.0, s[6] / seen if seen else math.nan,
                                 s[4] / seen if seen else math.nan, s[5])
     if difference is not None:
-        out.matched = int(first[14])
-        m = out.matched
-        out.mean_difference, out.rms_difference = (s[0] / m, math.sqrt(s[1] / m)) if m else (math.nan, math.nan)
-        out.min_difference, out.max_difference = s[2], s[3]
+        _fill_differences(out, int(first[14]), s[0:4])
     return out
 
 

@@ -60,6 +60,47 @@ def _mesh_arrays(mesh: ThermalMesh) -> Tuple[Tensor, Tensor, Tensor, int, int]:
     return p, t, tri, int(v), int(tri.shape[0])
 
 
+def _tree_arrays(bvh: "MeshBVH"):
+    """(positions, temperature, triangles, V, T, device, blob) after the checks every reader of the tree starts with"""
+    p, t, tri, v, n = _mesh_arrays(bvh.mesh)
+    if v != bvh.num_vertices or n != bvh.num_triangles:
+        raise ValueError("the tree belongs to another mesh: its vertex and face counts differ")
+    dev = p.device
+    blob = bvh.blob
+    if not isinstance(blob, Tensor) or not blob.is_cuda or blob.device != dev or not blob.is_contiguous():
+        raise ValueError("the tree's blob must be a contiguous tensor on the mesh's device")
+    return p, t, tri, v, n, dev, blob
+
+
+def _points(points: Tensor, letter: str, rows_only: bool = False) -> Tensor:
+    """the query points, [``letter``, 3] as the message names them; ``rows_only``: two dimensions are all a public call asks before
+    its ``*_into`` checks the rest"""
+    q = _hip.require_device_tensor(points, "points")
+    if q.dim() != 2 or not (rows_only or (q.shape[1] == 3 and 3 * q.shape[0] <= MAX_COUNT)):
+        raise ValueError(f"points must be [{letter}, 3] with 3 {letter} <= 2^31 - 1")
+    return q
+
+
+def _mesh_colors(mesh: ThermalMesh, v: int, dev) -> Tensor:
+    """``mesh.colors`` for a colour output; one placeholder row for a mesh without vertices, whose colours nothing reads"""
+    colors = _hip.require_device_tensor(mesh.colors, "colors", torch.uint8)
+    if colors.numel() != 3 * v or colors.device != dev:
+        raise ValueError("colors must be [V, 3] on the mesh's device")
+    return colors if v else torch.zeros((1, 3), dtype=torch.uint8, device=dev)
+
+
+def _moments(total: float, squares: float, count: int):
+    return (total / count, math.sqrt(squares / count)) if count else (math.nan, math.nan)
+
+
+def _fill_differences(out, matched: int, s) -> None:
+    """the five "differences" fields of ``ClosestPoints`` / ``ProjectedTemperatures`` from the host read: the points whose difference is
+    a number, and ``s`` = the ordered sum, the ordered sum of squares, the minimum and the maximum of the differences"""
+    out.matched = matched
+    out.mean_difference, out.rms_difference = _moments(s[0], s[1], matched)
+    out.min_difference, out.max_difference = s[2], s[3]
+
+
 @dataclasses.dataclass
 class MeshBVH:
     """what ``build_mesh_bvh`` made: the blob on the device with the mesh it belongs to.  The tree holds face INDICES and boxes: it
@@ -140,14 +181,7 @@ def mesh_raycast_into(bvh: MeshBVH, origins: Tensor, directions: Tensor, *, t_mi
     temperatures; needs ``hit_temperature``): each optional.  ``any_hit``: only ``hit_any`` uint8 [N] is written, 1 where the ray
     meets anything in its window."""
     check_window(float(t_min), float(t_max))
-    mesh = bvh.mesh
-    p, t, tri, v, n = _mesh_arrays(mesh)
-    if v != bvh.num_vertices or n != bvh.num_triangles:
-        raise ValueError("the tree belongs to another mesh: its vertex and face counts differ")
-    dev = p.device
-    blob = bvh.blob
-    if not isinstance(blob, Tensor) or not blob.is_cuda or blob.device != dev or not blob.is_contiguous():
-        raise ValueError("the tree's blob must be a contiguous tensor on the mesh's device")
+    p, t, tri, v, n, dev, blob = _tree_arrays(bvh)
     o, d, ray_t_max, rays = _rays(origins, directions, ray_t_max, dev)
     if any_hit:
         if hit_any is None:
@@ -156,13 +190,7 @@ def mesh_raycast_into(bvh: MeshBVH, origins: Tensor, directions: Tensor, *, t_mi
             raise ValueError("any_hit writes hit_any alone: the other outputs stay None")
     elif hit_any is not None:
         raise ValueError("hit_any is written with any_hit=True only")
-    colors = None
-    if hit_colors is not None:
-        colors = _hip.require_device_tensor(mesh.colors, "colors", torch.uint8)
-        if colors.numel() != 3 * v or colors.device != dev:
-            raise ValueError("colors must be [V, 3] on the mesh's device")
-        if v == 0:
-            colors = torch.zeros((1, 3), dtype=torch.uint8, device=dev)
+    colors = _mesh_colors(bvh.mesh, v, dev) if hit_colors is not None else None
     if stats is not None and hit_temperature is None:
         raise ValueError("stats are taken from hit_temperature: give both")
     hit_face = out_tensor(hit_face, "hit_face", torch.int32, rays, 1)
