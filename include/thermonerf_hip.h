@@ -1073,6 +1073,97 @@ int tn_mesh_project(const float *positions, const float *temperature, const int3
                     int64_t num_cameras, const tn_project_params *params, float *measured, int32_t *views, int32_t *best_camera,
                     float *spread, float *difference, int64_t *counts, double *stats, void *stream);
 
+/* Registration of a point cloud to the mesh: iterated closest points with a damped Gauss-Newton step, a whole run queued without a host
+ * read.  The fourth reader of tn_mesh_bvh_build's blob.  positions, temperature, triangles, V, T, bvh and bvh_bytes are the closest-point
+ * query's (temperature decides which faces are USABLE and is not read otherwise); points [N, 3] floats, the MOVING cloud, N = num_points,
+ * 3N <= 2^31 - 1; `params` is read on the HOST: max_distance = R >= 0, which may be +inf; center c and length L > 0, finite: the point the
+ * rotation and the scale act about, and the unit in which a translation is compared with the tolerance; damping >= 0, finite; tolerance
+ * >= 0, which may be +inf; 1 <= iterations <= 1024; metric TN_REGISTER_POINT or TN_REGISTER_PLANE; with_scale 0 or 1; min_pairs >= 0;
+ * reserved: write 0.  transform (DEVICE double [12], the row-major 3 x 4 matrix M that takes a point of the cloud into the mesh's frame)
+ * is read as the start and OVERWRITTEN with the result; history (device double [iterations, 4]), result (device int64 [4]) and the
+ * workspace are overwritten.  Every output is defined to the bit, and WITHOUT reference to the tree, in the ray cast's conventions: add /
+ * sub / mul / div / sqrt are single correctly rounded fp64 operations, nothing is contracted, no library function is called, (double) of a
+ * float is exact, dot and cross are the ray cast's, -x, |x|, max and mul by 0.5 are exact.
+ * ONE ITERATION i = 0, 1, ..., from the transform M as it is by then:
+ *   point j   p = (double) of its floats, x_k = add(add(add(mul(M[k][0], p0), mul(M[k][1], p1)), mul(M[k][2], p2)), M[k][3]).  USABLE when
+ *             the three floats and the three x_k are finite.
+ *   pair      of a usable point: the closest-point query's definition with Q = x — the fp64 numbers, NOT rounded to float — and
+ *             R2 = mul(R, R): the winner (face, C, d2) among the usable faces with d2 <= R2, the lowest face index on a tie.  The proof
+ *             given there holds for this Q as it stands: it uses only that sub, mul and add are monotone and that sub is odd, for
+ *             which Q may be any fp64 number; a sum that overflows becomes +inf on both sides of d2 >= b, and no NaN arises in d2 or b (C
+ *             is finite: u, v, s lie in [0, 1], and a NaN quotient fails the interior's test and gives an edge's s = +0.0).
+ *   rows      y = sub(x, c), e = sub(x, C), both per axis.  A direction n gives the row g = (cross(y, n), n, dot(n, y)), seven numbers,
+ *             and r = dot(n, e).  Metric POINT: three rows, n = (1, 0, 0), (0, 1, 0), (0, 0, 1) in this order, through the same cross
+ *             and dot (the products with 0 are taken, not skipped).  Metric PLANE: one row; e1 = sub(p1, p0), e2 = sub(p2, p0) of the
+ *             winning face, w = cross(e1, e2), nn = dot(w, w), n_k = div(w_k, sqrt(nn)).  A winner with nn == 0 is WITHOUT A NORMAL: the
+ *             point has no row and is counted.  A point is MATCHED when it has a row.
+ *   a point's 36 numbers   from +0.0 each, its rows in order: S[i][j] = add(S[i][j], mul(g_i, g_j)) for 0 <= i <= j < 7 (28 numbers,
+ *             row-major), then B[i] = add(B[i], mul(g_i, r)) (7), then E = add(E, mul(r, r)).  A point without a row holds 36 times +0.0.
+ *   wave w    the points 64 w .. 64 w + 63, beyond N as points without a row.  Each of the 36 numbers is summed over the wave's lanes
+ *             in the adjacent-pair tree: (0 + 1), (2 + 3), ..., (62 + 63), then adjacent pairs of these sums, six levels.  The wave's
+ *             PARTIAL is 40 doubles: the 36 sums, then its matched points, its usable points, its points without a normal as doubles,
+ *             then +0.0.  The partial of wave w is left at byte 64 + 320 w of the workspace (of the last iteration that ran).
+ *   totals    each of the 40 as SUM2 over the waves with runs of 256 (as tn_mesh_rasterize defines it): a run's waves ascending from
+ *             +0.0, then the runs' sums ascending from +0.0.  m = the matched points.
+ *   refusal   m < min_pairs: status TOO_FEW.
+ *   system    k = 7 with_scale, else 6: the leading k x k block of the symmetric S and the first k of B.  lambda = mul(damping, m),
+ *             L2 = mul(L, L); D[i] = add(S[i][i], mul(lambda, L2)) for i = 0, 1, 2, 6 and add(S[i][i], mul(lambda, 1)) for i = 3, 4, 5:
+ *             the damping is ADDITIVE, in units in which every unknown moves a point by about L.  Column by column, j = 0 .. k - 1:
+ *             d_j = D[j], then for p = 0 .. j - 1 ascending d_j = sub(d_j, mul(l[j][p], mul(l[j][p], d_p))); a d_j that is not > 0 or not
+ *             finite: status DEGENERATE; for i = j + 1 .. k - 1: v = S[j][i], for p = 0 .. j - 1 ascending v = sub(v, mul(l[i][p],
+ *             mul(l[j][p], d_p))), l[i][j] = div(v, d_j).  Then z_i = -B[i], for p = 0 .. i - 1 ascending z_i = sub(z_i, mul(l[i][p], z_p)),
+ *             i ascending; z_i = div(z_i, d_i); delta_i = z_i, for p = i + 1 .. k - 1 ascending delta_i = sub(delta_i, mul(l[p][i],
+ *             delta_p)), i DESCENDING.  A delta_i that is not finite: status DEGENERATE.  delta = (omega (3), tau (3), sigma); sigma = +0.0
+ *             without scale.
+ *   update    the Cayley map, no trigonometry: a = mul(0.5, omega), aa = dot(a, a), f = div(2, add(1, aa)); K = [a]x =
+ *             ((0, -a2, a1), (a2, 0, -a0), (-a1, a0, 0)) with +0.0 on the diagonal; Q[i][j] = mul(a_i, a_j) off the diagonal and
+ *             sub(mul(a_i, a_i), aa) on it; U[i][j] = mul(add(1, sigma), add(I[i][j], mul(f, add(K[i][j], Q[i][j])))).  New linear part
+ *             M'[i][j] = dot(U[i], column j of M's linear part); new translation M'[i][3] = add(add(c_i, dot(U[i], t - c)), tau_i) with
+ *             (t - c)_k = sub(M[k][3], c_k).  A refused iteration leaves M as it was.
+ *   history row i   (m, E, turn, shift): turn = max(|omega_0|, |omega_1|, |omega_2|, |sigma|), shift = div(max_k |tau_k|, L); -1.0 for
+ *             both in a refused iteration.  turn <= tolerance and shift <= tolerance: status CONVERGED (the update is applied).
+ *   A run ends with the first iteration whose status is CONVERGED, TOO_FEW or DEGENERATE; otherwise after `iterations` of them with
+ *   status ITERATIONS.  The history rows of iterations that did not run are four times -1.0.
+ *   result    [0] the status, [1] the iterations that ran, [2] m and [3] the usable points of the last one that ran.
+ * With N == 0 or T == 0 nothing is matched: TOO_FEW (min_pairs > 0) or DEGENERATE in iteration 0.
+ * Why the order is fixed: no sum is taken by an atomic; the wave's tree, the runs and the one thread's solve are written orders, so
+ * two calls, on any device state, write the same bytes.
+ * How: per iteration two launches.  The walk: one point per lane, blocks of one wave, the closest-point query's traversal (one
+ * definition in the source) from x; the 36 sums exist only after the walk, are reduced by lane exchanges and leave as one partial
+ * per wave.  The finish: one block sums the partials in the order above, one thread solves and writes M, the row and the result; a run
+ * that has ended sets a device flag on which the later iterations' kernels return at once.  The kernels check what they dereference as
+ * the closest-point query does.  Launches on `stream` only: iterations x (walk, finish) behind one memset of the flag; no allocation, no
+ * host synchronisation, no host read, no float atomics, no block waits for another.
+ * tn_mesh_register: TN_ERR_NULL: params, bvh, transform, history, result or workspace; TN_ERR_SHAPE: V, T out of range (as above),
+ * N < 0 or 3N > 2^31 - 1; TN_ERR_UNSUPPORTED: a parameter outside what is written above (a NaN fails each); TN_ERR_NULL: positions,
+ * temperature or triangles with V > 0 and T > 0; points with N > 0; TN_ERR_SHAPE: a float / int32 pointer not 4-byte aligned, transform
+ * / history / result / workspace not 8-byte aligned, bvh not 64-byte aligned; TN_ERR_WORKSPACE: bvh_bytes < tn_mesh_bvh_bytes(T) or
+ * workspace_bytes < tn_mesh_register_workspace_bytes(N) = 64 + 320 ceil(N / 64).  All are returned before any launch, in the siblings'
+ * order. */
+#define TN_REGISTER_POINT 0
+#define TN_REGISTER_PLANE 1
+#define TN_REGISTER_CONVERGED 0
+#define TN_REGISTER_ITERATIONS 1
+#define TN_REGISTER_TOO_FEW 2
+#define TN_REGISTER_DEGENERATE 3
+typedef struct tn_register_params {
+    double max_distance;
+    double center[3];
+    double length;
+    double damping;
+    double tolerance;
+    int32_t iterations;
+    int32_t metric;
+    int32_t with_scale;
+    int32_t min_pairs;
+    int32_t reserved[2];
+} tn_register_params;
+size_t tn_mesh_register_workspace_bytes(int64_t num_points);
+int tn_mesh_register(const float *positions, const float *temperature, const int32_t *triangles, int64_t num_vertices,
+                     int64_t num_triangles, const void *bvh, size_t bvh_bytes, const float *points, int64_t num_points,
+                     const tn_register_params *params, double *transform, double *history, int64_t *result, void *workspace,
+                     size_t workspace_bytes, void *stream);
+
 /* ------------------------------------------------------------------------------------------------------
  * Fused forward: Model.forward (collider) + ThermalNerfModel.get_outputs
  * [REF thermal_nerf_model.py:210-275]

@@ -118,6 +118,16 @@ class tn_project_params(C.Structure):
                 ("height", C.c_int32), ("two_sided", C.c_int32), ("reserved", C.c_int32)]
 
 
+class tn_register_params(C.Structure):
+    _fields_ = [("max_distance", C.c_double), ("center", C.c_double * 3), ("length", C.c_double), ("damping", C.c_double),
+                ("tolerance", C.c_double), ("iterations", C.c_int32), ("metric", C.c_int32), ("with_scale", C.c_int32),
+                ("min_pairs", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
+TN_REGISTER_POINT, TN_REGISTER_PLANE = 0, 1
+TN_REGISTER_STATUS = ("converged", "iterations", "too_few", "degenerate")  # the words of result[0]
+
+
 class tn_mesh_params(C.Structure):
     _fields_ = [("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("w2c", C.c_float * 12),
                 ("truncation", C.c_float), ("inv_truncation", C.c_float), ("min_accumulation", C.c_float), ("lo", C.c_float * 3),
@@ -289,6 +299,8 @@ SIGNATURES = {
     "tn_mesh_closest": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i64, _vp, _sz, _vp, _vp, _i64, C.POINTER(tn_closest_params)] + [_vp] * 10),
     "tn_mesh_project": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _vp, _sz, _vp, _vp, _vp, _i64, _vp, _vp, _i64, C.POINTER(tn_project_params)]
                         + [_vp] * 8),
+    "tn_mesh_register_workspace_bytes": (_sz, [_i64]),
+    "tn_mesh_register": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _vp, _sz, _vp, _i64, C.POINTER(tn_register_params), _vp, _vp, _vp, _vp, _sz, _vp]),
     "tn_mesh_tile": (_i32, []),
     "tn_mesh_scan_width": (_i32, []),
     "tn_mesh_workspace_bytes": (_sz, [_i32, _i32, _i32]),

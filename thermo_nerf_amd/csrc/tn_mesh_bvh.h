@@ -4,7 +4,8 @@
 // (walk: node unpack, nearer child first, the other on the LDS stack, overflow, the step guard — a reader supplies a box test and
 // a leaf test), the surface's values at (face, u, v), and the one statistics pass of the finish kernels (finish_one).
 // tn_mesh_bvh.hip builds the tree and casts rays through it, tn_mesh_closest.hip walks it for the nearest face, tn_mesh_project.hip
-// casts the occlusion rays of a projection: the slab and the face test are here for the two that cast.
+// casts the occlusion rays of a projection: the slab and the face test are here for the two that cast.  tn_mesh_register.hip walks it
+// for the nearest face of transformed points: what it shares with tn_mesh_closest.hip is in tn_mesh_closest.h.
 #pragma once
 #include "tn_device.h"
 

@@ -1,6 +1,6 @@
 """Export of a trained scene as 3-D data: a thermal point cloud (positions, colours, degrees per point; optionally without
 statistical outliers, down-sampled to one averaged point per voxel on a stable device sort, and with normals from a k-nearest-neighbour
-search on the device), a thermal triangle mesh (TSDF fusion + surface nets, degrees per vertex; optionally without its small connected components, simplified by vertex clustering, Taubin-smoothed, with vertex normals), the thermal regions of such a mesh (the patches warmer than X or colder than Y with their area, mean temperature and location), orthographic thermograms of a mesh (a scaled, distortion-free image through a z-buffered device rasteriser: the face, depth, temperature and colour of every pixel), ray queries against a mesh (a bounding-volume hierarchy built on the device and a traversal kernel: the view of a pinhole camera pixel for pixel, the temperature and the surface point behind a pixel, whether a point is visible from a camera), the nearest point of a mesh to any point through the same hierarchy (distances between clouds and meshes, and the per-vertex difference in degrees Celsius between two surveys as a mesh of its own), the measured thermal photos projected onto a mesh through that hierarchy (what the cameras measured at every vertex, from how many photos, how far they agree, and where the model differs) and their PLY files."""
+search on the device), a thermal triangle mesh (TSDF fusion + surface nets, degrees per vertex; optionally without its small connected components, simplified by vertex clustering, Taubin-smoothed, with vertex normals), the thermal regions of such a mesh (the patches warmer than X or colder than Y with their area, mean temperature and location), orthographic thermograms of a mesh (a scaled, distortion-free image through a z-buffered device rasteriser: the face, depth, temperature and colour of every pixel), ray queries against a mesh (a bounding-volume hierarchy built on the device and a traversal kernel: the view of a pinhole camera pixel for pixel, the temperature and the surface point behind a pixel, whether a point is visible from a camera), the nearest point of a mesh to any point through the same hierarchy (distances between clouds and meshes, and the per-vertex difference in degrees Celsius between two surveys as a mesh of its own), the measured thermal photos projected onto a mesh through that hierarchy (what the cameras measured at every vertex, from how many photos, how far they agree, and where the model differs) the registration of one survey's mesh into the frame of another's (iterated closest points on that hierarchy, the start from a few picked point pairs) and their PLY files."""
 from .closest import ClosestPoints, MeshDifference, mesh_closest, mesh_closest_into, mesh_difference  # noqa: F401
 from .components import (ComponentsInfo, MeshComponents, filter_components, mesh_components,  # noqa: F401
                          mesh_components_workspace_bytes, remove_small_components)
@@ -13,6 +13,8 @@ from .pointcloud import (PointCloudExporter, ThermalPointCloud, pointcloud_appen
                          subsample, subsample_indices, tile_rays, workspace_bytes, world_transform)
 from .project import (MeshMeasurement, ProjectedTemperatures, camera_records, mesh_measurement, project_images,  # noqa: F401
                       project_images_into)
+from .register import (Registration, register_mesh, register_points, register_points_into, register_workspace_bytes,  # noqa: F401
+                       similarity_from_pairs, transform_mesh)
 from .raycast import (CameraThermogram, CameraView, MeshBVH, RayHits, build_mesh_bvh, camera_rays, mesh_bvh_bytes,  # noqa: F401
                       mesh_bvh_depth_bound, mesh_bvh_workspace_bytes, mesh_camera_thermogram, mesh_raycast, mesh_raycast_into,
                       visible_from)
