@@ -5,6 +5,7 @@ command line and its report.  No GPU."""
 from __future__ import annotations
 
 import ctypes
+import dataclasses
 import importlib.util
 import json
 import math
@@ -16,6 +17,7 @@ import pytest
 import torch
 
 from tests import mesh_raycast_reference as R
+from tests import test_gpu_mesh_arguments as mesh_arguments
 from thermo_nerf_amd import _hip
 from thermo_nerf_amd.export import (CameraThermogram, CameraView, MeshBVH, ThermalMesh, build_mesh_bvh, camera_rays, mesh_bvh_bytes,
                                     mesh_bvh_depth_bound, mesh_bvh_workspace_bytes, mesh_camera_thermogram, mesh_raycast,
@@ -315,6 +317,18 @@ def test_python_layer_refuses_before_it_reaches_a_kernel():
     assert raycast_module.VISIBLE_FRACTION == 1.0 - 2.0 ** -10 and np.float32(raycast_module.VISIBLE_FRACTION) < 1.0
     with pytest.raises(ValueError, match="does not carry the header"):
         bvh.tree()
+
+
+@pytest.mark.parametrize("entry", list(mesh_arguments.ENTRIES))
+def test_every_mesh_entry_refuses_a_host_mesh_in_one_order(entry):
+    """the CPU half of tests/test_gpu_mesh_arguments.py: "no triangles" comes before "no CPU fallback", whichever entry is asked"""
+    mesh = mesh_arguments.quad("cpu")
+    bvh = MeshBVH(torch.zeros(192, dtype=torch.uint8), 4, 2, mesh)
+    call = mesh_arguments.ENTRIES[entry][0]
+    with pytest.raises(ValueError, match="the mesh has no triangles"):
+        call(dataclasses.replace(mesh, triangles=None), bvh, "cpu")
+    with pytest.raises(RuntimeError, match="no CPU fallback"):
+        call(mesh, bvh, "cpu")
 
 
 def _hand_made():

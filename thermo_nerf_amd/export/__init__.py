@@ -1,6 +1,20 @@
-"""Export of a trained scene as 3-D data: a thermal point cloud (positions, colours, degrees per point; optionally without
-statistical outliers, down-sampled to one averaged point per voxel on a stable device sort, and with normals from a k-nearest-neighbour
-search on the device), a thermal triangle mesh (TSDF fusion + surface nets, degrees per vertex; optionally without its small connected components, simplified by vertex clustering, Taubin-smoothed, with vertex normals), the thermal regions of such a mesh (the patches warmer than X or colder than Y with their area, mean temperature and location), orthographic thermograms of a mesh (a scaled, distortion-free image through a z-buffered device rasteriser: the face, depth, temperature and colour of every pixel), ray queries against a mesh (a bounding-volume hierarchy built on the device and a traversal kernel: the view of a pinhole camera pixel for pixel, the temperature and the surface point behind a pixel, whether a point is visible from a camera), the nearest point of a mesh to any point through the same hierarchy (distances between clouds and meshes, and the per-vertex difference in degrees Celsius between two surveys as a mesh of its own), the measured thermal photos projected onto a mesh through that hierarchy (what the cameras measured at every vertex, from how many photos, how far they agree, and where the model differs) the registration of one survey's mesh into the frame of another's (iterated closest points on that hierarchy, the start from a few picked point pairs) and their PLY files."""
+"""Export of a trained scene as 3-D data, and the analysis of what was exported; every module names its kernel.
+
+- pointcloud.py, neighbors.py, voxel.py: a thermal point cloud (positions, colours, degrees per point), its statistical outliers and
+  normals from a k-nearest-neighbour search, one averaged point per voxel on a stable device sort.
+- mesh.py, components.py, simplify.py, smooth.py: a thermal triangle mesh (TSDF fusion + surface nets, degrees per vertex), without
+  its small connected components, simplified by vertex clustering, Taubin-smoothed, with vertex normals.
+- regions.py: the patches of a mesh warmer than X or colder than Y with their area, mean temperature and location.
+- thermogram.py: orthographic thermograms through a z-buffered rasteriser: face, depth, temperature and colour per pixel.
+- raycast.py: a bounding-volume hierarchy built on the device and rays against it: a pinhole camera's view, what lies behind a
+  pixel, whether a point is visible from a camera.
+- closest.py: the nearest point of a mesh to any point through that hierarchy, and the per-vertex difference in degrees Celsius
+  between two surveys as a mesh of its own.
+- project.py: the measured thermal photos projected onto a mesh: what the cameras measured at every vertex, from how many photos,
+  how far they agree, where the model differs.
+- register.py: one survey's mesh into the frame of another's (iterated closest points, the start from a few picked pairs).
+- ply.py: their PLY files.  _common.py: the argument checks they share.  cli.py: what the command lines under tools/ share.
+"""
 from .closest import ClosestPoints, MeshDifference, mesh_closest, mesh_closest_into, mesh_difference  # noqa: F401
 from .components import (ComponentsInfo, MeshComponents, filter_components, mesh_components,  # noqa: F401
                          mesh_components_workspace_bytes, remove_small_components)

@@ -1,16 +1,20 @@
-"""What the export entry points share: the argument checks of the kernel wrappers (pointcloud.py, mesh.py, neighbors.py) and the
-pose loop of the two exporters — render camera after camera through one cached ``RayRenderEngine``, nothing synchronising
-between poses."""
+"""What the export entry points share: the argument checks of the kernel wrappers (pointcloud.py, mesh.py, neighbors.py), the checks
+of a ``ThermalMesh``, of a tree and of query points that every mesh analysis entry starts with, and the pose loop of the two
+exporters — render camera after camera through one cached ``RayRenderEngine``, nothing synchronising between poses."""
 from __future__ import annotations
 
 import dataclasses
+import math
 from typing import Iterator, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 from torch import Tensor
 
+from .. import _hip
+
 SCENE_BOX = "scene_box"
+MAX_COUNT = 2 ** 31 - 1  # vertices, triangles, points or the pairs of a sort: indices are int32
 _IDENTITY = (1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0)
 
 
@@ -36,6 +40,80 @@ def workspace_of(workspace: Optional[Tensor], need: int, device) -> Tuple[Tensor
     if not workspace.is_cuda or not workspace.is_contiguous() or size < need:
         raise ValueError(f"workspace must be a contiguous device tensor of at least {need} bytes")
     return workspace, size
+
+
+def triangle_array(triangles) -> Tensor:
+    """``triangles`` as every mesh kernel reads them: int32 [T, 3] on the device, 3 T within an int32"""
+    tri = _hip.require_device_tensor(triangles, "triangles", torch.int32)
+    if tri.dim() != 2 or tri.shape[1] != 3 or 3 * tri.shape[0] > MAX_COUNT:
+        raise ValueError("triangles must be [T, 3] with 3 T <= 2^31 - 1")
+    return tri
+
+
+def require_triangles(mesh) -> None:
+    """the first refusal of every mesh entry, for those that check their own parameters before the rest of ``mesh_arrays``"""
+    if mesh.triangles is None:
+        raise ValueError("the mesh has no triangles")
+
+
+def mesh_arrays(mesh, temperature: bool = True) -> Tuple[Tensor, Optional[Tensor], Tensor, int, int]:
+    """(positions, temperature, triangles, V, T) of a ``ThermalMesh`` after the checks every mesh entry starts with; without
+    ``temperature`` (an entry that reads the geometry alone) it is not looked at and comes back as None"""
+    require_triangles(mesh)
+    p =_hip.require_device_tensor(mesh.positions, "positions")
+    v = p.shape[0] if p.dim() == 2 and p.shape[1] == 3 else -1
+    if v < 0 or v > MAX_COUNT:
+        raise ValueError("positions must be [V, 3] with V <= 2^31 - 1")
+    t = _hip.require_device_tensor(mesh.temperature, "temperature") if temperature else None
+    tri = triangle_array(mesh.triangles)
+    if t is not None and t.numel() != v:
+        raise ValueError("temperature must hold V values")
+    if tri.device != p.device or (t is not None and t.device != p.device):
+        raise ValueError("positions, temperature and triangles must be on one device")
+    return p, t, tri, int(v), int(tri.shape[0])
+
+
+def color_array(colors, name: str, v: int, dev) -> Tensor:
+    """a mesh's ``colors`` or ``thermal_colors`` for an entry that reads them: uint8 [V, 3]; one placeholder row for a mesh without
+    vertices, whose colours nothing reads (an empty tensor has no address)"""
+    c = _hip.require_device_tensor(colors, name, torch.uint8)
+    if tuple(c.shape) != (v, 3) or c.device != dev:
+        raise ValueError(f"{name} must be [V, 3] on the mesh's device")
+    return c if v else torch.zeros((1, 3), dtype=torch.uint8, device=dev)
+
+
+def tree_arrays(bvh):
+    """(positions, temperature, triangles, V, T, device, blob) of a ``MeshBVH`` after the checks every reader of the tree starts with"""
+    p, t, tri, v, n = mesh_arrays(bvh.mesh)
+    if v != bvh.num_vertices or n != bvh.num_triangles:
+        raise ValueError("the tree belongs to another mesh: its vertex and face counts differ")
+    dev = p.device
+    blob = bvh.blob
+    if not isinstance(blob, Tensor) or not blob.is_cuda or blob.device != dev or not blob.is_contiguous():
+        raise ValueError("the tree's blob must be a contiguous tensor on the mesh's device")
+    return p, t, tri, v, n, dev, blob
+
+
+def query_points(points: Tensor, letter: str, rows_only: bool = False) -> Tensor:
+    """the query points, [``letter``, 3] as the message names them; ``rows_only``: two dimensions are all a public call asks before
+    its ``*_into`` checks the rest"""
+    q = _hip.require_device_tensor(points, "points")
+    if q.dim() != 2 or not (rows_only or (q.shape[1] == 3 and 3 * q.shape[0] <= MAX_COUNT)):
+        raise ValueError(f"points must be [{letter}, 3] with 3 {letter} <= 2^31 - 1")
+    return q
+
+
+def moments(total: float, squares: float, count: int) -> Tuple[float, float]:
+    """(mean, root mean square) from the sum, the sum of squares and the count; NaN without a value"""
+    return (total / count, math.sqrt(squares / count)) if count else (math.nan, math.nan)
+
+
+def fill_differences(out, matched: int, s) -> None:
+    """the five "differences" fields of ``ClosestPoints`` / ``ProjectedTemperatures`` from the host read: the points whose difference is
+    a number, and ``s`` = the ordered sum, the ordered sum of squares, the minimum and the maximum of the differences"""
+    out.matched = matched
+    out.mean_difference, out.rms_difference = moments(s[0], s[1], matched)
+    out.min_difference, out.max_difference = s[2], s[3]
 
 
 def affine12(to_world) -> Tuple[float, ...]:

@@ -18,9 +18,9 @@ import torch
 from torch import Tensor
 
 from .. import _hip
-from ._common import out_tensor
+from ._common import color_array, fill_differences, mesh_arrays, moments, out_tensor, query_points, tree_arrays
 from .mesh import ThermalMesh
-from .raycast import MeshBVH, _fill_differences, _mesh_colors, _moments, _points, _tree_arrays
+from .raycast import MeshBVH
 
 
 def check_max_distance(max_distance: float) -> None:
@@ -42,8 +42,8 @@ def mesh_closest_into(bvh: MeshBVH, points: Tensor, *, max_distance: float = mat
     ``stats`` float64 [8] (ordered sum, ordered sum of squares, minimum, maximum of the distances, then of the differences; needs
     ``closest_distance``): each optional."""
     check_max_distance(float(max_distance))
-    p, t, tri, v, n, dev, blob = _tree_arrays(bvh)
-    q = _points(points, "N")
+    p, t, tri, v, n, dev, blob = tree_arrays(bvh)
+    q = query_points(points, "N")
     if q.device != dev:
         raise ValueError("the points must be on the mesh's device")
     count = int(q.shape[0])
@@ -51,7 +51,7 @@ def mesh_closest_into(bvh: MeshBVH, points: Tensor, *, max_distance: float = mat
         point_temperature = _hip.require_device_tensor(point_temperature, "point_temperature")
         if point_temperature.numel() != count or point_temperature.device != dev:
             raise ValueError("point_temperature must hold N values on the mesh's device")
-    colors = _mesh_colors(bvh.mesh, v, dev) if closest_colors is not None else None
+    colors = color_array(bvh.mesh.colors, "colors", v, dev) if closest_colors is not None else None
     if difference is not None and (point_temperature is None or closest_temperature is None):
         raise ValueError("difference is point_temperature - closest_temperature: give both")
     if stats is not None and closest_distance is None:
@@ -65,6 +65,8 @@ def mesh_closest_into(bvh: MeshBVH, points: Tensor, *, max_distance: float = mat
     difference = out_tensor(difference, "difference", torch.float32, count, 1)
     counts = out_tensor(counts, "counts", torch.int64, 4, 1)
     stats = out_tensor(stats, "stats", torch.float64, 8, 1)
+    if stats is not None and closest_distance.numel() == 0:  # no point: an empty tensor has no address, and NULL means "not given"
+        closest_distance = closest_distance.new_empty((1,))
     params = _hip.tn_closest_params(float(max_distance))
     work = v > 0 and n > 0
     with torch.cuda.device(dev):
@@ -111,7 +113,7 @@ def mesh_closest(bvh: MeshBVH, points: Tensor, *, max_distance: float = math.inf
     check_max_distance(float(max_distance))
     p = _hip.require_device_tensor(bvh.mesh.positions, "positions")
     dev = p.device
-    n = int(_points(points, "N", rows_only=True).shape[0])
+    n = int(query_points(points, "N", rows_only=True).shape[0])
     with torch.cuda.device(dev):
         head = torch.zeros((13,), dtype=torch.int64, device=dev)  # the four counts, the eight statistics, the matched points
         face = torch.empty((n,), dtype=torch.int32, device=dev)
@@ -127,11 +129,11 @@ def mesh_closest(bvh: MeshBVH, points: Tensor, *, max_distance: float = math.inf
         first = head.cpu().numpy()  # the one read
     found, usable_points, usable_faces, limit = (int(x) for x in first[:4])
     s = [float(x) for x in first[4:12].view(np.float64)]
-    mean, rms = _moments(s[0], s[1], found)
+    mean, rms = moments(s[0], s[1], found)
     out = ClosestPoints(face, distance, where, uv, temperature, colors, difference, found, usable_points, usable_faces, limit, mean, rms,
                         s[2], s[3])
     if difference is not None:
-        _fill_differences(out, int(first[12]), s[4:8])
+        fill_differences(out, int(first[12]), s[4:8])
     return out
 
 
@@ -162,12 +164,7 @@ def mesh_difference(mesh: ThermalMesh, reference_bvh: MeshBVH, *, max_distance: 
     matched).  A NaN vertex makes its faces unusable for ``thermal_regions`` and the rasteriser: the parts of ``mesh`` without a
     counterpart are left out of every area, region and image of the difference.  One host read."""
     check_max_distance(float(max_distance))
-    if mesh.triangles is None:
-        raise ValueError("the mesh has no triangles")
-    points = _hip.require_device_tensor(mesh.positions, "positions")
-    own = _hip.require_device_tensor(mesh.temperature, "temperature")
-    if points.dim() != 2 or points.shape[1] != 3 or own.numel() != points.shape[0]:
-        raise ValueError("positions must be [V, 3] and temperature must hold V values")
+    points, own, _, _, _ = mesh_arrays(mesh)
     found = mesh_closest(reference_bvh, points, max_distance=max_distance, point_temperature=own.reshape(-1))
     m = max(abs(found.min_difference), abs(found.max_difference)) if found.matched else None
     delta = ThermalMesh(mesh.positions, mesh.colors, found.difference, None, mesh.triangles, None if m is None else (-m, m), mesh.normals)

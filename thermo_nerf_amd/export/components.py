@@ -15,10 +15,8 @@ import torch
 from torch import Tensor
 
 from .. import _hip
-from ._common import out_tensor, workspace_of
+from ._common import MAX_COUNT, out_tensor, triangle_array, workspace_of
 from .mesh import ThermalMesh
-
-MAX_COUNT = 2 ** 31 - 1  # vertices or triangles: indices are int32
 
 
 class MeshComponents(NamedTuple):
@@ -46,12 +44,10 @@ def mesh_components_workspace_bytes(num_vertices: int, num_triangles: int) -> in
 
 
 def _triangles(triangles: Tensor, num_vertices: int) -> Tuple[Tensor, int, int]:
-    t = _hip.require_device_tensor(triangles, "triangles", torch.int32)
-    if t.dim() != 2 or t.shape[1] != 3:
-        raise ValueError("triangles must be [T, 3]")
+    t = triangle_array(triangles)
     v = int(num_vertices)
-    if not 0 <= v <= MAX_COUNT or t.shape[0] > MAX_COUNT:
-        raise ValueError("num_vertices and the number of triangles must be 0 .. 2^31 - 1")
+    if not 0 <= v <= MAX_COUNT:
+        raise ValueError("num_vertices must be 0 .. 2^31 - 1")
     return t, int(t.shape[0]), v
 
 

@@ -19,9 +19,9 @@ import torch
 from torch import Tensor
 
 from .. import _hip
-from ._common import out_tensor
+from ._common import fill_differences, mesh_arrays, out_tensor, query_points, tree_arrays
 from .mesh import ThermalMesh
-from .raycast import CameraView, MeshBVH, _fill_differences, _points, _tree_arrays, check_camera
+from .raycast import CameraView, MeshBVH, check_camera
 from .smooth import vertex_normals
 from .thermogram import MAX_SIDE
 
@@ -74,8 +74,8 @@ def project_images_into(bvh: MeshBVH, points: Tensor, normals: Optional[Tensor],
     sum, sum of squares, minimum, maximum of the differences; sum and maximum of the spreads; sum of the measurements; 0 — each from
     its output array): each optional."""
     lo, hi = check_projection(temperature_bounds, float(min_cos), float(near))
-    p, t, tri, v, n, dev, blob = _tree_arrays(bvh)
-    q = _points(points, "P")
+    p, t, tri, v, n, dev, blob = tree_arrays(bvh)
+    q = query_points(points, "P")
     count = int(q.shape[0])
     if normals is not None:
         normals = _hip.require_device_tensor(normals, "normals")
@@ -156,7 +156,7 @@ def project_images(bvh: MeshBVH, points: Tensor, normals: Optional[Tensor], came
     records, width, height = camera_records(cameras)
     p = _hip.require_device_tensor(bvh.mesh.positions, "positions")
     dev = p.device
-    n = int(_points(points, "P", rows_only=True).shape[0])
+    n = int(query_points(points, "P", rows_only=True).shape[0])
     photos = _hip.require_device_tensor(images, "images", torch.uint8)
     if photos.dim() != 3 or photos.shape[0] != len(records) or (len(records) and tuple(photos.shape[1:]) != (height, width)):
         raise ValueError(f"images must be uint8 [K, H, W] = [{len(records)}, {height}, {width}] like the views, got {tuple(photos.shape)}")
@@ -178,7 +178,7 @@ def project_images(bvh: MeshBVH, points: Tensor, normals: Optional[Tensor], came
                                 seen / n if n else 0.0, accepted / n if n else 0.0, s[6] / seen if seen else math.nan,
                                 s[4] / seen if seen else math.nan, s[5])
     if difference is not None:
-        _fill_differences(out, int(first[14]), s[0:4])
+        fill_differences(out, int(first[14]), s[0:4])
     return out
 
 
@@ -211,13 +211,8 @@ def mesh_measurement(mesh: ThermalMesh, bvh: MeshBVH, cameras: Sequence[CameraVi
     A NaN vertex makes its faces unusable for ``thermal_regions`` and the rasteriser: the parts of ``mesh`` that no photo shows are
     left out of every area, region and image of either mesh.  One host read."""
     lo, hi = check_projection(temperature_bounds, float(min_cos), float(near))
-    if mesh.triangles is None:
-        raise ValueError("the mesh has no triangles")
-    points = _hip.require_device_tensor(mesh.positions, "positions")
-    own = _hip.require_device_tensor(mesh.temperature, "temperature")
-    if points.dim() != 2 or points.shape[1] != 3 or own.numel() != points.shape[0]:
-        raise ValueError("positions must be [V, 3] and temperature must hold V values")
-    normals = mesh.normals if mesh.normals is not None else vertex_normals(points, mesh.triangles)
+    points, own, triangles, _, _ = mesh_arrays(mesh)
+    normals = mesh.normals if mesh.normals is not None else vertex_normals(points, triangles)
     got = project_images(bvh, points, normals, cameras, images, (lo, hi), point_temperature=own.reshape(-1), min_cos=min_cos, near=near,
                          two_sided=two_sided)
     m = max(abs(got.min_difference), abs(got.max_difference)) if got.matched else None

@@ -16,12 +16,10 @@ import numpy as np
 import torch
 from torch import Tensor
 
-from .. import _hip, colormaps
-from ._common import out_tensor, workspace_of
-from .components import MAX_COUNT
+from .. import _hip
+from ._common import MAX_COUNT, color_array, mesh_arrays, out_tensor, tree_arrays, workspace_of
 from .mesh import ThermalMesh
-from .regions import ThermalRegions
-from .thermogram import MAX_SIDE, thermal_bounds
+from .thermogram import MAX_SIDE, PixelImage
 
 STACK_ENTRIES = 64  # per ray; the depth bound of the tree is 61
 # ``visible_from`` stops every ray at this fraction of the way to its point: 2^-10 of the distance short of it, so that the
@@ -39,66 +37,6 @@ def mesh_bvh_bytes(num_triangles: int) -> int:
 
 def mesh_bvh_workspace_bytes(num_triangles: int) -> int:
     return int(_hip.load().tn_mesh_bvh_workspace_bytes(int(num_triangles)))
-
-
-def _mesh_arrays(mesh: ThermalMesh) -> Tuple[Tensor, Tensor, Tensor, int, int]:
-    """(positions, temperature, triangles, V, T) after the checks every entry starts with"""
-    if mesh.triangles is None:
-        raise ValueError("the mesh has no triangles")
-    p = _hip.require_device_tensor(mesh.positions, "positions")
-    v = p.shape[0] if p.dim() == 2 and p.shape[1] == 3 else -1
-    if v < 0 or v > MAX_COUNT:
-        raise ValueError("positions must be [V, 3] with V <= 2^31 - 1")
-    t = _hip.require_device_tensor(mesh.temperature, "temperature")
-    tri = _hip.require_device_tensor(mesh.triangles, "triangles", torch.int32)
-    if t.numel() != v:
-        raise ValueError("temperature must hold V values")
-    if tri.dim() != 2 or tri.shape[1] != 3 or 3 * tri.shape[0] > MAX_COUNT:
-        raise ValueError("triangles must be [T, 3] with 3 T <= 2^31 - 1")
-    if tri.device != p.device or t.device != p.device:
-        raise ValueError("positions, temperature and triangles must be on one device")
-    return p, t, tri, int(v), int(tri.shape[0])
-
-
-def _tree_arrays(bvh: "MeshBVH"):
-    """(positions, temperature, triangles, V, T, device, blob) after the checks every reader of the tree starts with"""
-    p, t, tri, v, n = _mesh_arrays(bvh.mesh)
-    if v != bvh.num_vertices or n != bvh.num_triangles:
-        raise ValueError("the tree belongs to another mesh: its vertex and face counts differ")
-    dev = p.device
-    blob = bvh.blob
-    if not isinstance(blob, Tensor) or not blob.is_cuda or blob.device != dev or not blob.is_contiguous():
-        raise ValueError("the tree's blob must be a contiguous tensor on the mesh's device")
-    return p, t, tri, v, n, dev, blob
-
-
-def _points(points: Tensor, letter: str, rows_only: bool = False) -> Tensor:
-    """the query points, [``letter``, 3] as the message names them; ``rows_only``: two dimensions are all a public call asks before
-    its ``*_into`` checks the rest"""
-    q = _hip.require_device_tensor(points, "points")
-    if q.dim() != 2 or not (rows_only or (q.shape[1] == 3 and 3 * q.shape[0] <= MAX_COUNT)):
-        raise ValueError(f"points must be [{letter}, 3] with 3 {letter} <= 2^31 - 1")
-    return q
-
-
-def _mesh_colors(mesh: ThermalMesh, v: int, dev) -> Tensor:
-    """``mesh.colors`` for a colour output; one placeholder row for a mesh without vertices, whose colours nothing reads"""
-    colors = _hip.require_device_tensor(mesh.colors, "colors", torch.uint8)
-    if colors.numel() != 3 * v or colors.device != dev:
-        raise ValueError("colors must be [V, 3] on the mesh's device")
-    return colors if v else torch.zeros((1, 3), dtype=torch.uint8, device=dev)
-
-
-def _moments(total: float, squares: float, count: int):
-    return (total / count, math.sqrt(squares / count)) if count else (math.nan, math.nan)
-
-
-def _fill_differences(out, matched: int, s) -> None:
-    """the five "differences" fields of ``ClosestPoints`` / ``ProjectedTemperatures`` from the host read: the points whose difference is
-    a number, and ``s`` = the ordered sum, the ordered sum of squares, the minimum and the maximum of the differences"""
-    out.matched = matched
-    out.mean_difference, out.rms_difference = _moments(s[0], s[1], matched)
-    out.min_difference, out.max_difference = s[2], s[3]
 
 
 @dataclasses.dataclass
@@ -134,7 +72,7 @@ class MeshBVH:
 def build_mesh_bvh(mesh: ThermalMesh, *, blob: Optional[Tensor] = None, workspace: Optional[Tensor] = None) -> MeshBVH:
     """``tn_mesh_bvh_build`` on the current stream, without a host synchronisation: the tree of ``mesh``'s usable faces.  ``blob``:
     ``mesh_bvh_bytes(T)`` device bytes to build into (allocated if absent); ``workspace``: ``mesh_bvh_workspace_bytes(T)``."""
-    p, t, tri, v, n = _mesh_arrays(mesh)
+    p, t, tri, v, n = mesh_arrays(mesh)
     dev = p.device
     with torch.cuda.device(dev):
         blob, blob_size = workspace_of(blob, mesh_bvh_bytes(n), dev)
@@ -181,7 +119,7 @@ def mesh_raycast_into(bvh: MeshBVH, origins: Tensor, directions: Tensor, *, t_mi
     temperatures; needs ``hit_temperature``): each optional.  ``any_hit``: only ``hit_any`` uint8 [N] is written, 1 where the ray
     meets anything in its window."""
     check_window(float(t_min), float(t_max))
-    p, t, tri, v, n, dev, blob = _tree_arrays(bvh)
+    p, t, tri, v, n, dev, blob = tree_arrays(bvh)
     o, d, ray_t_max, rays = _rays(origins, directions, ray_t_max, dev)
     if any_hit:
         if hit_any is None:
@@ -190,7 +128,7 @@ def mesh_raycast_into(bvh: MeshBVH, origins: Tensor, directions: Tensor, *, t_mi
             raise ValueError("any_hit writes hit_any alone: the other outputs stay None")
     elif hit_any is not None:
         raise ValueError("hit_any is written with any_hit=True only")
-    colors = _mesh_colors(bvh.mesh, v, dev) if hit_colors is not None else None
+    colors = color_array(bvh.mesh.colors, "colors", v, dev) if hit_colors is not None else None
     if stats is not None and hit_temperature is None:
         raise ValueError("stats are taken from hit_temperature: give both")
     hit_face = out_tensor(hit_face, "hit_face", torch.int32, rays, 1)
@@ -320,8 +258,9 @@ def camera_rays(camera: CameraView, device) -> Tuple[Tensor, Tensor]:
 
 
 @dataclasses.dataclass
-class CameraThermogram:
-    """what ``mesh_camera_thermogram`` made: the four images on the device and the numbers of the one host read"""
+class CameraThermogram(PixelImage):
+    """what ``mesh_camera_thermogram`` made: the four images on the device and the numbers of the one host read; ``to_rgb8`` and
+    ``region_map`` are ``PixelImage``'s"""
 
     pixel_face: Tensor          # int32 [H, W]: the face every pixel shows, -1 where empty
     pixel_distance: Tensor      # float32 [H, W]: the distance from the camera centre along the pixel's ray, NaN where empty
@@ -338,40 +277,11 @@ class CameraThermogram:
     stack_limit_rays: int
     temperature_bounds: Optional[Tuple[float, float]] = None  # the mesh's
 
-    def to_rgb8(self, colors: str = "thermal", bounds: Optional[Tuple[float, float]] = None) -> Tensor:
-        """uint8 [H, W, 3] on the device, as ``Thermogram.to_rgb8``: ``"rgb"`` the mesh's colours, ``"thermal"`` the temperatures
-        through the magma table over ``bounds``, the mesh's ``temperature_bounds`` or the image's own range.  Empty pixels are black."""
-        if colors == "rgb":
-            if self.pixel_colors is None:
-                raise ValueError("the mesh has no colours")
-            return self.pixel_colors
-        if colors != "thermal":
-            raise ValueError('colors is "thermal" or "rgb"')
-        from ..render.renderer import LUT, frame_to_rgb8
-
-        lo, hi = thermal_bounds(bounds, self.temperature_bounds, (self.min_temperature, self.max_temperature))
-        t = self.pixel_temperature
-        x = (t - lo) / (hi - lo) if hi > lo else torch.where(torch.isnan(t), t, torch.zeros_like(t))
-        table = torch.from_numpy(colormaps.table_u8("magma")).to(t.device).contiguous()
-        height, width = t.shape
-        return frame_to_rgb8(x.reshape(-1, 1).contiguous(), LUT, table).reshape(height, width, 3)
-
     def world_position(self, row: int, col: int) -> Tuple[float, float, float]:
         """origin + distance direction of pixel (row, col): where the surface it shows lies (one host read; NaN where empty)"""
         k = int(row) * int(self.camera.width) + int(col)
         o, d = self.origins[k].double(), self.directions[k].double()
         return tuple(float(x) for x in (o + self.pixel_distance[int(row), int(col)].double() * d).cpu())
-
-    def region_map(self, regions: ThermalRegions) -> Tensor:
-        """int32 [H, W]: ``regions.face_region`` gathered through ``pixel_face`` — the number of the thermal region every pixel
-        shows, -1 where the pixel is empty or its face lies in no region"""
-        face_region = regions.face_region
-        if face_region.device != self.pixel_face.device:
-            raise ValueError("the regions and the thermogram are on different devices")
-        if bool((self.pixel_face >= face_region.shape[0]).any()):
-            raise ValueError("the regions belong to another mesh: a pixel shows a face beyond face_region")
-        padded = torch.cat([face_region, torch.full((1,), -1, dtype=face_region.dtype, device=face_region.device)])
-        return padded[self.pixel_face.long()]
 
 
 @torch.no_grad()

@@ -17,8 +17,7 @@ import torch
 from torch import Tensor
 
 from .. import _hip
-from ._common import out_tensor, workspace_of
-from .components import MAX_COUNT
+from ._common import mesh_arrays, out_tensor, require_triangles, workspace_of
 from .mesh import ThermalMesh
 
 # a row of the region table: tn_mesh_region, field for field (72 bytes, no padding)
@@ -71,22 +70,9 @@ def mesh_regions_into(mesh: ThermalMesh, min_temperature: float, max_temperature
     [T] (required when the mesh has faces); ``regions``: a uint8 device tensor of ``REGION_BYTES`` per row, read on the host as
     ``REGION_DTYPE``; ``face_area``: float64 [T], optional.  ``capacity_regions`` defaults to the rows ``regions`` can hold (0
     without it: the sizing call).  ``workspace``: ``mesh_regions_workspace_bytes(V, T)`` device bytes (allocated if absent)."""
-    if mesh.triangles is None:
-        raise ValueError("the mesh has no triangles")
+    require_triangles(mesh)
     lo, hi = _window(min_temperature, max_temperature)
-    p = _hip.require_device_tensor(mesh.positions, "positions")
-    v = p.shape[0] if p.dim() == 2 and p.shape[1] == 3 else -1
-    if v < 0 or v > MAX_COUNT:
-        raise ValueError("positions must be [V, 3] with V <= 2^31 - 1")
-    t = _hip.require_device_tensor(mesh.temperature, "temperature")
-    tri = _hip.require_device_tensor(mesh.triangles, "triangles", torch.int32)
-    if t.numel() != v:
-        raise ValueError("temperature must hold V values")
-    if tri.dim() != 2 or tri.shape[1] != 3 or 3 * tri.shape[0] > MAX_COUNT:
-        raise ValueError("triangles must be [T, 3] with 3 T <= 2^31 - 1")
-    if tri.device != p.device or t.device != p.device:
-        raise ValueError("positions, temperature and triangles must be on one device")
-    n = int(tri.shape[0])
+    p, t, tri, v, n = mesh_arrays(mesh)
     if regions is not None and (not isinstance(regions, Tensor) or regions.dtype != torch.uint8):
         raise ValueError("regions must be a uint8 device tensor")
     cap = int(regions.numel() // REGION_BYTES if regions is not None else 0) if capacity_regions is None else int(capacity_regions)
@@ -134,14 +120,11 @@ def thermal_regions(mesh: ThermalMesh, min_temperature: float = -math.inf, max_t
     a face's temperature is the mean of its three vertices; faces that share a vertex are one region).  Regions of no area are
     dropped, so are those below ``min_area`` (in the mesh's units squared); the rest come largest first, ties by ascending label,
     cut to ``top``.  Two host reads: the counts with the two areas, then the R rows."""
-    if mesh.triangles is None:
-        raise ValueError("the mesh has no triangles")
+    require_triangles(mesh)
     window = _window(min_temperature, max_temperature)
     order_regions(np.zeros(0, REGION_DTYPE), min_area, top)  # the refusals, before anything runs
-    p = _hip.require_device_tensor(mesh.positions, "positions")
-    if p.dim() != 2 or p.shape[1] != 3:
-        raise ValueError("positions must be [V, 3]")
-    v, t, dev = int(p.shape[0]), int(mesh.triangles.shape[0]), p.device
+    p, _, _, v, t = mesh_arrays(mesh)
+    dev = p.device
     cap = max_regions(v, t)
     with torch.cuda.device(dev):
         head = torch.empty((5,), dtype=torch.int64, device=dev)  # the three counts and, behind them, the two areas
@@ -161,8 +144,7 @@ def thermal_regions(mesh: ThermalMesh, min_temperature: float = -math.inf, max_t
 def regions_mesh(mesh: ThermalMesh, regions: ThermalRegions) -> ThermalMesh:
     """The faces of the kept regions as a mesh of their own: faces in face order, the vertices they name in ascending index, every
     attribute carried (normals too); ``write_mesh_ply`` writes it.  Torch indexing on the device."""
-    if mesh.triangles is None:
-        raise ValueError("the mesh has no triangles")
+    require_triangles(mesh)
     tri, face_region = mesh.triangles, regions.face_region
     if face_region.shape[0] != tri.shape[0]:
         raise ValueError("the regions belong to another mesh: face_region and triangles differ in length")

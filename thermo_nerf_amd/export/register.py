@@ -19,10 +19,10 @@ import torch
 from torch import Tensor
 
 from .. import _hip
-from ._common import out_tensor
+from ._common import mesh_arrays, out_tensor, query_points, tree_arrays
 from .closest import check_max_distance
 from .mesh import ThermalMesh
-from .raycast import MeshBVH, _points, _tree_arrays
+from .raycast import MeshBVH
 
 METRICS = {"point": _hip.TN_REGISTER_POINT, "plane": _hip.TN_REGISTER_PLANE}
 MAX_ITERATIONS = 1024
@@ -65,8 +65,8 @@ def register_points_into(bvh: MeshBVH, points: Tensor, transform: Tensor, histor
     iteration (-1 where none ran), ``result`` int64 [4] the status, the iterations run, the matched and the usable points of the
     last.  ``workspace``: uint8, at least ``register_workspace_bytes(N)``; allocated when absent."""
     check_register_params(max_distance, center, float(length), float(damping), float(tolerance), iterations, metric, min_pairs)
-    p, t, tri, v, n, dev, blob = _tree_arrays(bvh)
-    q = _points(points, "N")
+    p, t, tri, v, n, dev, blob = tree_arrays(bvh)
+    q = query_points(points, "N")
     if q.device != dev:
         raise ValueError("the points must be on the mesh's device")
     count = int(q.shape[0])
@@ -138,8 +138,8 @@ def register_points(bvh: MeshBVH, points: Tensor, *, initial=None, max_distance:
     if not radii:
         raise ValueError("max_distance must be a number or a non-empty sequence of numbers")
     start = _as_matrix(initial)
-    p, t, tri, v, n, dev, blob = _tree_arrays(bvh)
-    q = _points(points, "N")
+    p, t, tri, v, n, dev, blob = tree_arrays(bvh)
+    q = query_points(points, "N")
     count = int(q.shape[0])
     if center is None or length is None:
         box = bvh.tree()
@@ -183,9 +183,7 @@ def register_mesh(mesh: ThermalMesh, reference_bvh: MeshBVH, *, max_points: Opti
     s = ceil(V / max_points).  The options are ``register_points``'s."""
     if max_points is not None and int(max_points) < 1:
         raise ValueError(f"max_points must be >= 1, got {max_points}")
-    points = _hip.require_device_tensor(mesh.positions, "positions")
-    if points.dim() != 2 or points.shape[1] != 3:
-        raise ValueError("positions must be [V, 3]")
+    points = mesh_arrays(mesh, temperature=False)[0]
     if max_points is not None:
         stride = -(-int(points.shape[0]) // int(max_points))
         if stride > 1:

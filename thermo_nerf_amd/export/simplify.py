@@ -20,8 +20,7 @@ import torch
 from torch import Tensor
 
 from .. import _hip
-from ._common import out_tensor, workspace_of
-from .components import MAX_COUNT
+from ._common import color_array, mesh_arrays, out_tensor, require_triangles, workspace_of
 from .mesh import ThermalMesh
 from .voxel import voxel_grid, voxel_params
 
@@ -43,6 +42,14 @@ def mesh_simplify_workspace_bytes(num_vertices: int, num_triangles: int) -> int:
     return int(_hip.load().tn_mesh_simplify_workspace_bytes(int(num_vertices), int(num_triangles)))
 
 
+def _simplify_arrays(mesh: ThermalMesh):
+    """(positions, colors, temperature, thermal_colors or None, triangles, V, T): ``mesh_arrays`` and the colours the kernel averages"""
+    p, t, tri, v, n = mesh_arrays(mesh)
+    c = color_array(mesh.colors, "colors", v, p.device)
+    tc = None if mesh.thermal_colors is None else color_array(mesh.thermal_colors, "thermal_colors", v, p.device)
+    return p, c, t, tc, tri, v, n
+
+
 def mesh_simplify_into(mesh: ThermalMesh, params, *, counts: Tensor, positions: Optional[Tensor] = None, colors: Optional[Tensor] = None,
                        temperature: Optional[Tensor] = None, cluster_count: Optional[Tensor] = None,
                        thermal_colors: Optional[Tensor] = None, triangles: Optional[Tensor] = None,
@@ -56,23 +63,7 @@ def mesh_simplify_into(mesh: ThermalMesh, params, *, counts: Tensor, positions: 
     triangles, triangles dropped as invalid or degenerate and triangles dropped as duplicates.  The capacities default to the rows
     of ``positions`` / ``triangles`` (0 without them: the sizing call).  ``workspace``: ``mesh_simplify_workspace_bytes(V, T)``
     device bytes (allocated if absent)."""
-    if mesh.triangles is None:
-        raise ValueError("the mesh has no triangles")
-    p = _hip.require_device_tensor(mesh.positions, "positions")
-    v = p.shape[0] if p.dim() == 2 and p.shape[1] == 3 else -1
-    if v < 0 or v > MAX_COUNT:
-        raise ValueError("positions must be [V, 3] with V <= 2^31 - 1")
-    c = _hip.require_device_tensor(mesh.colors, "colors", torch.uint8)
-    t = _hip.require_device_tensor(mesh.temperature, "temperature")
-    tc = None if mesh.thermal_colors is None else _hip.require_device_tensor(mesh.thermal_colors, "thermal_colors", torch.uint8)
-    tri = _hip.require_device_tensor(mesh.triangles, "triangles", torch.int32)
-    if tuple(c.shape) != (v, 3) or t.numel() != v or (tc is not None and tuple(tc.shape) != (v, 3)):
-        raise ValueError("colors / thermal_colors must be [V, 3] and temperature must hold V values")
-    if tri.dim() != 2 or tri.shape[1] != 3 or 3 * tri.shape[0] > MAX_COUNT:
-        raise ValueError("triangles must be [T, 3] with 3 T <= 2^31 - 1")
-    if tri.device != p.device:
-        raise ValueError("positions and triangles must be on one device")
-    n = int(tri.shape[0])
+    p, c, t, tc, tri, v, n = _simplify_arrays(mesh)
     cap_v = int(positions.shape[0] if positions is not None else 0) if capacity_vertices is None else int(capacity_vertices)
     cap_t = int(triangles.shape[0] if triangles is not None else 0) if capacity_triangles is None else int(capacity_triangles)
     if cap_v < 0 or cap_t < 0:
@@ -129,13 +120,10 @@ def simplify_mesh(mesh: ThermalMesh, cell_size: float) -> Tuple[ThermalMesh, Sim
     (``voxel_grid``, as ``voxel_downsample``).  Normals, if present, are dropped (they would be stale; compute them afterwards);
     ``temperature_bounds`` is carried over.  Two host reads: the six numbers of the bounding box, then the four counts.  Returns
     (the simplified mesh, ``SimplifyInfo``).  A ``cell_size`` that needs more than 2^21 cells on an axis raises ``ValueError``."""
-    if mesh.triangles is None:
-        raise ValueError("the mesh has no triangles")
+    require_triangles(mesh)
     size = _cell_size(cell_size)
-    p = _hip.require_device_tensor(mesh.positions, "positions")
-    if p.dim() != 2 or p.shape[1] != 3:
-        raise ValueError("positions must be [V, 3]")
-    v, t, dev = int(p.shape[0]), int(mesh.triangles.shape[0]), p.device
+    p, _, _, _, _, v, t = _simplify_arrays(mesh)
+    dev = p.device
     if v == 0:
         return _empty(mesh, (v, t), t)
     with torch.cuda.device(dev):

@@ -17,7 +17,7 @@ from torch import Tensor
 
 from .. import _hip
 from ._common import workspace_of
-from .components import MAX_COUNT, _triangles
+from .components import _triangles
 from .mesh import ThermalMesh
 
 
@@ -34,18 +34,11 @@ def mesh_incidence_workspace_bytes(num_vertices: int, num_triangles: int) -> int
     return int(_hip.load().tn_mesh_incidence_workspace_bytes(int(num_vertices), int(num_triangles)))
 
 
-def _mesh(triangles: Tensor, num_vertices: int) -> Tuple[Tensor, int, int]:
-    tri, t, v = _triangles(triangles, num_vertices)
-    if 3 * t > MAX_COUNT:
-        raise ValueError("three times the number of triangles must not exceed 2^31 - 1")
-    return tri, t, v
-
-
 def mesh_incidence(triangles: Tensor, num_vertices: int, workspace: Optional[Tensor] = None) -> MeshIncidence:
     """The incidence index of ``triangles`` ([T,3] int32 on the device) over ``num_vertices`` vertices through
     ``tn_mesh_incidence``, on the current stream, without a host synchronisation.  ``workspace``:
     ``mesh_incidence_workspace_bytes(V, T)`` device bytes (allocated if absent)."""
-    tri, t, v = _mesh(triangles, num_vertices)
+    tri, t, v = _triangles(triangles, num_vertices)
     dev = tri.device
     workspace, workspace_size = workspace_of(workspace, mesh_incidence_workspace_bytes(v, t), dev)
     with torch.cuda.device(dev):
@@ -62,7 +55,7 @@ def _indexed(positions: Tensor, triangles: Tensor, incidence: Optional[MeshIncid
     pos = _hip.require_device_tensor(positions, "positions")
     if pos.dim() != 2 or pos.shape[1] != 3:
         raise ValueError("positions must be [V, 3]")
-    tri, t, v = _mesh(triangles, int(pos.shape[0]))
+    tri, t, v = _triangles(triangles, int(pos.shape[0]))
     if tri.device != pos.device:
         raise ValueError("positions and triangles must be on one device")
     if incidence is None:

@@ -16,8 +16,7 @@ import torch
 from torch import Tensor
 
 from .. import _hip, colormaps
-from ._common import out_tensor, workspace_of
-from .components import MAX_COUNT
+from ._common import color_array, mesh_arrays, out_tensor, require_triangles, workspace_of
 from .mesh import ThermalMesh
 from .regions import ThermalRegions
 
@@ -162,29 +161,11 @@ def mesh_rasterize_into(mesh: ThermalMesh, view: RasterView, *, counts: Tensor, 
     ordered sum of the pixels' temperatures, their minimum and maximum; ``pixel_face`` int32, ``pixel_depth`` and
     ``pixel_temperature`` float32 [H, W], ``pixel_colors`` uint8 [H, W, 3] (from ``mesh.colors``): each optional.  ``workspace``:
     ``mesh_rasterize_workspace_bytes(T, W, H)`` device bytes (allocated if absent).  ``small_box``: measurements only."""
-    if mesh.triangles is None:
-        raise ValueError("the mesh has no triangles")
+    require_triangles(mesh)
     check_view(view)
-    p = _hip.require_device_tensor(mesh.positions, "positions")
-    v = p.shape[0] if p.dim() == 2 and p.shape[1] == 3 else -1
-    if v < 0 or v > MAX_COUNT:
-        raise ValueError("positions must be [V, 3] with V <= 2^31 - 1")
-    t = _hip.require_device_tensor(mesh.temperature, "temperature")
-    tri = _hip.require_device_tensor(mesh.triangles, "triangles", torch.int32)
-    if t.numel() != v:
-        raise ValueError("temperature must hold V values")
-    if tri.dim() != 2 or tri.shape[1] != 3 or 3 * tri.shape[0] > MAX_COUNT:
-        raise ValueError("triangles must be [T, 3] with 3 T <= 2^31 - 1")
-    if tri.device != p.device or t.device != p.device:
-        raise ValueError("positions, temperature and triangles must be on one device")
-    colors = None
-    if pixel_colors is not None:
-        colors = _hip.require_device_tensor(mesh.colors, "colors", torch.uint8)
-        if colors.numel() != 3 * v or colors.device != p.device:
-            raise ValueError("colors must be [V, 3] on the mesh's device")
-        if v == 0:  # pixel_colors asks for a colour array, and an empty tensor has no address
-            colors = torch.zeros((1, 3), dtype=torch.uint8, device=p.device)
-    n, pixels = int(tri.shape[0]), int(view.width) * int(view.height)
+    p, t, tri, v, n = mesh_arrays(mesh)
+    colors = color_array(mesh.colors, "colors", v, p.device) if pixel_colors is not None else None
+    pixels = int(view.width) * int(view.height)
     pixel_face = out_tensor(pixel_face, "pixel_face", torch.int32, pixels, 1)
     pixel_depth = out_tensor(pixel_depth, "pixel_depth", torch.float32, pixels, 1)
     pixel_temperature = out_tensor(pixel_temperature, "pixel_temperature", torch.float32, pixels, 1)
@@ -204,9 +185,45 @@ def mesh_rasterize_into(mesh: ThermalMesh, view: RasterView, *, counts: Tensor, 
             stats.data_ptr(), workspace.data_ptr() if work else None, size, _hip.current_stream()), "tn_mesh_rasterize")
 
 
+class PixelImage:
+    """what ``Thermogram`` and ``CameraThermogram`` do alike with their images ``pixel_face``, ``pixel_temperature`` and
+    ``pixel_colors`` [H, W], the mesh's ``temperature_bounds`` and the image's ``min_temperature`` / ``max_temperature``"""
+
+    def to_rgb8(self, colors: str = "thermal", bounds: Optional[Tuple[float, float]] = None) -> Tensor:
+        """uint8 [H, W, 3] on the device.  ``"rgb"``: the mesh's colours.  ``"thermal"``: (t - lo) / (hi - lo) through
+        ``tn_frame_to_rgb8``'s ``TN_FRAME_LUT`` with the magma table; ``bounds`` = (lo, hi) defaults to the mesh's
+        ``temperature_bounds``, then to the image's own range.  Empty pixels come out black."""
+        if colors == "rgb":
+            if self.pixel_colors is None:
+                raise ValueError("the mesh has no colours")
+            return self.pixel_colors
+        if colors != "thermal":
+            raise ValueError('colors is "thermal" or "rgb"')
+        from ..render.renderer import LUT, frame_to_rgb8
+
+        lo, hi = thermal_bounds(bounds, self.temperature_bounds, (self.min_temperature, self.max_temperature))
+        t = self.pixel_temperature
+        x = (t - lo) / (hi - lo) if hi > lo else torch.where(torch.isnan(t), t, torch.zeros_like(t))
+        table = torch.from_numpy(colormaps.table_u8("magma")).to(t.device).contiguous()
+        height, width = t.shape
+        return frame_to_rgb8(x.reshape(-1, 1).contiguous(), LUT, table).reshape(height, width, 3)
+
+    def region_map(self, regions: ThermalRegions) -> Tensor:
+        """int32 [H, W]: ``regions.face_region`` gathered through ``pixel_face`` — the number of the thermal region every pixel
+        shows, -1 where the pixel is empty or its face lies in no region"""
+        face_region = regions.face_region
+        if face_region.device != self.pixel_face.device:
+            raise ValueError("the regions and the thermogram are on different devices")
+        if bool((self.pixel_face >= face_region.shape[0]).any()):
+            raise ValueError("the regions belong to another mesh: a pixel shows a face beyond face_region")
+        padded = torch.cat([face_region, torch.full((1,), -1, dtype=face_region.dtype, device=face_region.device)])
+        return padded[self.pixel_face.long()]  # (the last slot takes the -1 of the empty pixels)
+
+
 @dataclasses.dataclass
-class Thermogram:
-    """what ``mesh_thermogram`` made: the four images on the device and the numbers of the one host read"""
+class Thermogram(PixelImage):
+    """what ``mesh_thermogram`` made: the four images on the device and the numbers of the one host read; ``to_rgb8`` and
+    ``region_map`` are ``PixelImage``'s"""
 
     pixel_face: Tensor          # int32 [H, W]: the face every pixel shows, -1 where empty
     pixel_depth: Tensor         # float32 [H, W]: its depth along ``view.forward`` from the image plane, NaN where empty
@@ -222,39 +239,11 @@ class Thermogram:
     usable_faces: int
     temperature_bounds: Optional[Tuple[float, float]] = None  # the mesh's
 
-    def to_rgb8(self, colors: str = "thermal", bounds: Optional[Tuple[float, float]] = None) -> Tensor:
-        """uint8 [H, W, 3] on the device.  ``"rgb"``: the mesh's colours.  ``"thermal"``: (t - lo) / (hi - lo) through
-        ``tn_frame_to_rgb8``'s ``TN_FRAME_LUT`` with the magma table; ``bounds`` = (lo, hi) defaults to the mesh's
-        ``temperature_bounds``, then to the image's own range.  Empty pixels come out black."""
-        if colors == "rgb":
-            return self.pixel_colors
-        if colors != "thermal":
-            raise ValueError('colors is "thermal" or "rgb"')
-        from ..render.renderer import LUT, frame_to_rgb8
-
-        lo, hi = thermal_bounds(bounds, self.temperature_bounds, (self.min_temperature, self.max_temperature))
-        t = self.pixel_temperature
-        x = (t - lo) / (hi - lo) if hi > lo else torch.where(torch.isnan(t), t, torch.zeros_like(t))
-        table = torch.from_numpy(colormaps.table_u8("magma")).to(t.device).contiguous()
-        height, width = t.shape
-        return frame_to_rgb8(x.reshape(-1, 1).contiguous(), LUT, table).reshape(height, width, 3)
-
     def world_position(self, row: int, col: int) -> Tuple[float, float, float]:
         """origin + (col + 0.5) s right + (row + 0.5) s down + depth forward: where the surface that pixel (row, col) shows lies (one
         host read; NaN where the pixel is empty)"""
         v = self.view
         return pixel_position(v, int(row), int(col), float(self.pixel_depth[int(row), int(col)]))
-
-    def region_map(self, regions: ThermalRegions) -> Tensor:
-        """int32 [H, W]: ``regions.face_region`` gathered through ``pixel_face`` — the number of the thermal region every pixel
-        shows, -1 where the pixel is empty or its face lies in no region"""
-        face_region = regions.face_region
-        if face_region.device != self.pixel_face.device:
-            raise ValueError("the regions and the thermogram are on different devices")
-        if bool((self.pixel_face >= face_region.shape[0]).any()):
-            raise ValueError("the regions belong to another mesh: a pixel shows a face beyond face_region")
-        padded = torch.cat([face_region, torch.full((1,), -1, dtype=face_region.dtype, device=face_region.device)])
-        return padded[self.pixel_face.long()]  # (the last slot takes the -1 of the empty pixels)
 
 
 def thermal_bounds(given, of_mesh, of_image) -> Tuple[float, float]:

@@ -16,10 +16,9 @@ import torch
 from torch import Tensor
 
 from .. import _hip
-from ._common import out_tensor, workspace_of
+from ._common import MAX_COUNT, out_tensor, workspace_of
 from .pointcloud import ThermalPointCloud
 
-MAX_COUNT = 2 ** 31 - 1   # points, or pairs of a sort: indices are int32
 MAX_VOXELS_PER_AXIS = 2 ** 21
 
 

@@ -35,6 +35,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from mesh_scenes import event_ms  # noqa: E402
+
 ROUTES = ("render", "export", "extract")
 MAX_T, MIN_T = 33.0, 14.0
 
@@ -128,26 +130,6 @@ def main() -> int:
         with open(args.smooth_out, "w") as f:
             f.write(report)
     return 0
-
-
-def event_ms(fn, repeats: int, calls: int):
-    """(median, min, max) ms per call of ``fn``: 3 warm-up calls, then ``repeats`` event windows of ``calls`` calls each"""
-    import torch
-
-    for _ in range(3):
-        fn()
-    torch.cuda.synchronize()
-    per_call = []
-    for _ in range(repeats):
-        start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        start.record()
-        for _ in range(calls):
-            fn()
-        end.record()
-        end.synchronize()
-        per_call.append(start.elapsed_time(end) / calls)
-    per_call.sort()
-    return per_call[len(per_call) // 2], per_call[0], per_call[-1]
 
 
 def extract_call_of(exporter, volume, mesh):

@@ -23,7 +23,6 @@ degrees, the distance, the face and the world position behind that pixel.  One s
 from __future__ import annotations
 
 import argparse
-import importlib.util
 import json
 import math
 import os
@@ -34,16 +33,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
-INTRINSICS = ("fl_x", "fl_y", "cx", "cy", "w", "h")
-
-
-def _regions_tool():
-    """tools/mesh_regions.py: the helpers shared with it (``file_bounds``)"""
-    spec = importlib.util.spec_from_file_location("mesh_regions_tool", os.path.join(ROOT, "tools", "mesh_regions.py"))
-    module = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(module)
-    return module
-
+from thermo_nerf_amd.export.cli import frame_camera, json_number, load_mesh_ply, require_rocm_device, write_report  # noqa: E402,F401
 
 def parse(argv=None) -> argparse.Namespace:
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
@@ -88,44 +78,6 @@ def find_frame(meta: dict, wanted: str) -> int:
     return index
 
 
-def frame_camera(meta: dict, index: int, scale: float = 1.0) -> dict:
-    """{"c2w": 3 x 4 rows, "fx", "fy", "cx", "cy", "width", "height"} of frame ``index``: the intrinsics from the file's top level,
-    else from the frame (the dataparser's rule); the pose as written with ``applied_transform`` and ``applied_scale`` undone; the
-    image size and the intrinsics times ``scale`` (the size truncated, as ``Cameras.rescale_output_resolution`` does)"""
-    import numpy as np
-
-    if meta.get("camera_model", "OPENCV") not in ("OPENCV", "PINHOLE", "SIMPLE_PINHOLE"):
-        raise ValueError(f"camera_model {meta['camera_model']}: only perspective cameras")
-    frame = meta["frames"][index]
-    values = {}
-    for k in INTRINSICS:
-        if k in meta:
-            values[k] = float(meta[k])
-        elif k in frame:
-            values[k] = float(frame[k])
-        else:
-            raise ValueError(f"{k} is neither in the file nor in the frame")
-    pose = np.asarray(frame["transform_matrix"], dtype=np.float64)
-    if pose.shape == (3, 4):
-        pose = np.concatenate([pose, [[0.0, 0.0, 0.0, 1.0]]])
-    if pose.shape != (4, 4) or not np.isfinite(pose).all():
-        raise ValueError("transform_matrix is a finite 4 x 4 (or 3 x 4) matrix")
-    if "applied_transform" in meta:
-        applied = np.concatenate([np.asarray(meta["applied_transform"], dtype=np.float64).reshape(3, 4), [[0.0, 0.0, 0.0, 1.0]]])
-        pose = np.linalg.inv(applied) @ pose
-    if "applied_scale" in meta:
-        pose[:3, 3] /= float(meta["applied_scale"])
-    width, height = int(values["w"] * scale), int(values["h"] * scale)
-    if width < 1 or height < 1:
-        raise ValueError(f"--scale {scale} leaves an image of {width} x {height} pixels")
-    return {"c2w": pose[:3].tolist(), "fx": values["fl_x"] * scale, "fy": values["fl_y"] * scale, "cx": values["cx"] * scale,
-            "cy": values["cy"] * scale, "width": width, "height": height}
-
-
-def _bound(x: float):
-    return None if math.isinf(x) or math.isnan(x) else float(x)
-
-
 def pixel_record(camera: dict, origins, directions, temperature, face, distance, row: int, col: int) -> dict:
     """what lies behind pixel (row, col), over host arrays: ``origins`` / ``directions`` [H W, 3], the images [H, W]"""
     k = row * int(camera["width"]) + col
@@ -156,8 +108,8 @@ def build_report(camera: dict, frame_name: str, frame_index: int, found, origins
             "counts": {"vertices": int(num_vertices), "faces": int(num_faces), "usable_faces": int(found.usable_faces), "pixels": pixels,
                        "covered_pixels": int(found.covered), "stack_limit_rays": int(found.stack_limit_rays)},
             "covered_share": float(found.covered) / pixels,
-            "mean_temperature": _bound(found.mean_temperature), "min_temperature": _bound(found.min_temperature),
-            "max_temperature": _bound(found.max_temperature), "hottest_pixel": hottest, "coldest_pixel": coldest}
+            "mean_temperature": json_number(found.mean_temperature), "min_temperature": json_number(found.min_temperature),
+            "max_temperature": json_number(found.max_temperature), "hottest_pixel": hottest, "coldest_pixel": coldest}
 
 
 def summary_line(report: dict, source) -> str:
@@ -181,10 +133,9 @@ def main(argv=None) -> int:
     args = parse(argv)
 
     import numpy as np
-    import torch
     from PIL import Image
 
-    from thermo_nerf_amd.export import CameraView, ThermalMesh, build_mesh_bvh, mesh_camera_thermogram, read_mesh_ply
+    from thermo_nerf_amd.export import CameraView, build_mesh_bvh, mesh_camera_thermogram
 
     meta = json.loads(args.transforms.read_text())
     index = find_frame(meta, args.frame)
@@ -192,13 +143,7 @@ def main(argv=None) -> int:
     for row, col in args.probe:
         if row >= camera["height"] or col >= camera["width"]:
             raise ValueError(f"--probe {row} {col}: the image has {camera['height']} rows and {camera['width']} columns")
-    data = read_mesh_ply(args.mesh)
-    dev = torch.device(args.device)
-    if dev.type != "cuda":
-        raise RuntimeError(f"--device {args.device}: thermo_nerf_amd casts rays only on a ROCm device (no CPU fallback exists)")
-    bounds = _regions_tool().file_bounds(data["comments"])
-    mesh = ThermalMesh(torch.from_numpy(data["positions"].copy()).to(dev), torch.from_numpy(data["colors"].copy()).to(dev),
-                       torch.from_numpy(data["temperature"].copy()).to(dev), None, torch.from_numpy(data["triangles"].copy()).to(dev), bounds)
+    mesh, data = load_mesh_ply(args.mesh, require_rocm_device(args.device, "casts rays"), with_bounds=True)
     view = CameraView(camera["c2w"], camera["fx"], camera["fy"], camera["cx"], camera["cy"], camera["width"], camera["height"])
     found = mesh_camera_thermogram(build_mesh_bvh(mesh), view, cull=args.cull_back)
     image = found.to_rgb8(args.colors).cpu().numpy()
@@ -217,8 +162,7 @@ def main(argv=None) -> int:
         with open(args.temperatures, "wb") as f:  # (np.save given a name would append .npy to one without it)
             np.save(f, temperature)
     if args.report is not None:
-        args.report.parent.mkdir(parents=True, exist_ok=True)
-        args.report.write_text(json.dumps(report, indent=1) + "\n")
+        write_report(args.report, report, say=False)
     return 0
 
 

@@ -12,20 +12,9 @@ same number of camera rays on the same mesh and tree, timed in the same run — 
 from __future__ import annotations
 
 import argparse
-import importlib.util
-import os
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-if ROOT not in sys.path:
-    sys.path.insert(0, ROOT)
-
-
-def _tool(name: str):
-    spec = importlib.util.spec_from_file_location(name, os.path.join(ROOT, "tools", name + ".py"))
-    module = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(module)
-    return module
+import mesh_scenes  # the sibling module: the scenes, event_ms, emit; it puts the repository on sys.path
 
 
 def main() -> int:
@@ -39,14 +28,13 @@ def main() -> int:
 
     import torch
 
-    from thermo_nerf_amd.export import (CameraView, ThermalMesh, build_mesh_bvh, camera_rays, mesh_closest_into, mesh_raycast_into)
+    from thermo_nerf_amd.export import ThermalMesh, build_mesh_bvh, camera_rays, mesh_closest_into, mesh_raycast_into
 
-    cast_bench = _tool("mesh_raycast_bench")
-    event_ms = _tool("mesh_simplify_bench").event_ms
+    event_ms, cell = mesh_scenes.event_ms, mesh_scenes.cell
     dev = torch.device("cuda")
     w, h = args.width, args.height
     n = w * h
-    camera = CameraView(cast_bench.look_at((5.4, 3.5, 2.3), (1.6, 1.2, 0.5)), 0.8 * w, 0.8 * w, w / 2.0, h / 2.0, w, h)
+    camera = mesh_scenes.room_camera(w, h)
     origins, directions = camera_rays(camera, dev)
     face = torch.empty((n,), dtype=torch.int32, device=dev)
     distance, temperature, difference = torch.empty((n,), device=dev), torch.empty((n,), device=dev), torch.empty((n,), device=dev)
@@ -67,7 +55,7 @@ def main() -> int:
              "cast ms                         Mrays/s   near / cast   uniform / cast"]
     rows = []
     for cells in args.cells:
-        pos, temp, col, tri = cast_bench.room(cells, 1, dev)
+        pos, temp, col, tri = mesh_scenes.room(cells, 1, dev)
         mesh = ThermalMesh(pos, col, temp, None, tri)
         faces = int(tri.shape[0])
         bvh = build_mesh_bvh(mesh)
@@ -88,9 +76,6 @@ def main() -> int:
         cast = event_ms(lambda: mesh_raycast_into(bvh, origins, directions, hit_face=face, hit_t=distance, hit_uv=uv, hit_temperature=temperature,
                                                   hit_colors=colors, counts=counts, stats=cast_stats), args.repeats)
 
-        def cell(ms):
-            return f"{ms[0]:8.4f} ({ms[1]:.4f} .. {ms[2]:.4f})"
-
         (a, da), (b, db) = found
         lines.append(f"{faces:<10d} {depth:<7d} {cell(a):<31s} {n / a[0] / 1e3:<10.1f} {da:<11.5f} {cell(b):<31s} {n / b[0] / 1e3:<10.1f} {db:<11.5f} "
                      f"{cell(cast):<31s} {n / cast[0] / 1e3:<9.1f} {a[0] / cast[0]:<13.2f} {b[0] / cast[0]:.2f}")
@@ -100,12 +85,7 @@ def main() -> int:
         (f0, a0, b0, c0), (f1, a1, b1, c1) = rows[0], rows[-1]
         lines.append(f"at {f1} faces / at {f0} faces ({f1 / f0:.2f} x the faces): near-surface {a1 / a0:.2f} x, uniform {b1 / b0:.2f} x, "
                      f"cast {c1 / c0:.2f} x (medians above)")
-    report = "\n".join(lines) + "\n"
-    print(report)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write(report)
+    mesh_scenes.emit(lines, args.out)
     return 0
 
 

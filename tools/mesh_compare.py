@@ -19,7 +19,6 @@ are in the meshes' own units.
 from __future__ import annotations
 
 import argparse
-import json
 import math
 import os
 import sys
@@ -28,6 +27,9 @@ from pathlib import Path
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
+
+from thermo_nerf_amd.export.cli import (add_difference_regions, difference_region_lines, json_number, load_mesh_ply,  # noqa: E402,F401
+                                        region_rows, require_rocm_device, write_report)
 
 
 def parse(argv=None) -> argparse.Namespace:
@@ -50,19 +52,6 @@ def parse(argv=None) -> argparse.Namespace:
     return args
 
 
-def _number(x):
-    """a float for JSON: None for what JSON cannot say (NaN, the infinities, an absent value)"""
-    return None if x is None or not math.isfinite(float(x)) else float(x)
-
-
-def region_rows(found, warmed: bool, length_scale: float = 1.0) -> list:
-    """the rows of a ``ThermalRegions`` of the difference mesh: area, mean difference, centroid, the largest change of a face"""
-    s = float(length_scale)
-    return [{"region": int(r), "faces": int(row["faces"]), "area": float(row["area"]) * s * s, "mean_difference": float(row["mean_temperature"]),
-             "largest_change": float(row["max_temperature"] if warmed else row["min_temperature"]),
-             "centroid": [float(c) * s for c in row["centroid"]]} for r, row in zip(found.region_index.tolist(), found.regions)]
-
-
 def build_report(found, vertices, faces, reference_vertices, reference_faces, max_distance: float, length_scale: float = 1.0,
                  warmed=None, cooled=None, min_change=None, source: str = "", reference: str = "") -> dict:
     """the JSON report of ``found`` (a ``MeshDifference``): plain Python numbers, None where there is no value; distances times
@@ -70,23 +59,19 @@ def build_report(found, vertices, faces, reference_vertices, reference_faces, ma
     s = float(length_scale)
 
     def length(x):
-        x = _number(x)
+        x = json_number(x)
         return None if x is None else x * s
 
-    report = {"mesh": source, "reference": reference, "length_scale": s, "max_distance": _number(max_distance),
+    report = {"mesh": source, "reference": reference, "length_scale": s, "max_distance": json_number(max_distance),
               "counts": {"vertices": int(vertices), "faces": int(faces), "reference_vertices": int(reference_vertices),
                          "reference_faces": int(reference_faces), "reference_usable_faces": int(found.closest.usable_faces),
                          "matched_vertices": int(found.matched), "stack_limit_points": int(found.closest.stack_limit_points)},
               "matched_share": float(found.matched_share),
               "distance": {"mean": length(found.mean_distance), "rms": length(found.rms_distance), "max": length(found.max_distance)},
-              "difference": {"mean": _number(found.mean_difference), "rms": _number(found.rms_difference),
-                             "min": _number(found.min_difference), "max": _number(found.max_difference)}}
+              "difference": {"mean": json_number(found.mean_difference), "rms": json_number(found.rms_difference),
+                             "min": json_number(found.min_difference), "max": json_number(found.max_difference)}}
     if min_change is not None:
-        report["min_change"] = float(min_change)
-        for name, regions, sign in (("warmed", warmed, True), ("cooled", cooled, False)):
-            report[name] = {"regions": region_rows(regions, sign, s), "area": float(regions.selected_area) * s * s,
-                            "share": float(regions.selected_area / regions.mesh_area) if regions.mesh_area > 0.0 else 0.0}
-        report["compared_area"] = float(warmed.mesh_area) * s * s
+        add_difference_regions(report, ("warmed", "cooled"), warmed, cooled, min_change, s)
     return report
 
 
@@ -100,41 +85,17 @@ def summary_line(report: dict) -> str:
 
 
 def region_lines(report: dict) -> list:
-    lines = []
-    for name in ("warmed", "cooled"):
-        for k, row in enumerate(report.get(name, {}).get("regions", [])):
-            c = row["centroid"]
-            lines.append(f"{name} {k}: area {row['area']:.6g}, {row['faces']} faces, mean {row['mean_difference']:+.2f} C, largest "
-                         f"{row['largest_change']:+.2f} C, centroid ({c[0]:.4g}, {c[1]:.4g}, {c[2]:.4g})")
-    return lines
-
-
-def load_mesh(path, dev):
-    """(the ``ThermalMesh`` of a PLY on ``dev``, its host arrays)"""
-    import torch
-
-    from thermo_nerf_amd.export import ThermalMesh, read_mesh_ply
-
-    data = read_mesh_ply(path)
-    normals = data.get("normals")
-    mesh = ThermalMesh(torch.from_numpy(data["positions"].copy()).to(dev), torch.from_numpy(data["colors"].copy()).to(dev),
-                       torch.from_numpy(data["temperature"].copy()).to(dev), None, torch.from_numpy(data["triangles"].copy()).to(dev),
-                       None, None if normals is None else torch.from_numpy(normals.copy()).to(dev))
-    return mesh, data
+    return difference_region_lines(report, ("warmed", "cooled"))
 
 
 def main(argv=None) -> int:
     args = parse(argv)
 
-    import torch
-
     from thermo_nerf_amd.export import build_mesh_bvh, mesh_difference, thermal_regions, write_mesh_ply
 
-    dev = torch.device(args.device)
-    if dev.type != "cuda":
-        raise RuntimeError(f"--device {args.device}: thermo_nerf_amd compares meshes only on a ROCm device (no CPU fallback exists)")
-    mesh, data = load_mesh(args.mesh, dev)
-    reference, reference_data = load_mesh(args.reference, dev)
+    dev = require_rocm_device(args.device, "compares meshes")
+    mesh, data = load_mesh_ply(args.mesh, dev, with_bounds=False)
+    reference, reference_data = load_mesh_ply(args.reference, dev, with_bounds=False)
     found = mesh_difference(mesh, build_mesh_bvh(reference), max_distance=args.max_distance)
     warmed = cooled = None
     if args.min_change is not None:
@@ -145,9 +106,7 @@ def main(argv=None) -> int:
     print(summary_line(report))
     for line in region_lines(report):
         print(line)
-    args.report.parent.mkdir(parents=True, exist_ok=True)
-    args.report.write_text(json.dumps(report, indent=1) + "\n")
-    print(f"wrote {args.report}")
+    write_report(args.report, report)
     write_mesh_ply(args.output, found.mesh)
     print(f"wrote {args.output}: vertices {len(found.mesh)}, triangles {int(found.mesh.triangles.shape[0])}")
     return 0

@@ -29,7 +29,6 @@ X below (``thermal_regions`` on the residual mesh, as ``tools/mesh_compare.py`` 
 from __future__ import annotations
 
 import argparse
-import importlib.util
 import json
 import math
 import os
@@ -40,13 +39,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
-
-def _tool(name: str):
-    """another command line of tools/: the helpers shared with it"""
-    spec = importlib.util.spec_from_file_location(f"{name}_tool", os.path.join(ROOT, "tools", f"{name}.py"))
-    module = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(module)
-    return module
+from thermo_nerf_amd.export.cli import (add_difference_regions, difference_region_lines, file_bounds, frame_camera,  # noqa: E402
+                                        json_number, load_mesh_ply, require_rocm_device, write_report)
 
 
 def parse(argv=None) -> argparse.Namespace:
@@ -112,11 +106,6 @@ def load_photos(meta: dict, index, data_dir: Path, width: int, height: int):
     return photos
 
 
-def _number(x):
-    """a float for JSON: None for what JSON cannot say (NaN, the infinities, an absent value)"""
-    return None if x is None or not math.isfinite(float(x)) else float(x)
-
-
 def build_report(found, vertices, faces, frames, width, height, bounds, min_cos: float, two_sided: bool, length_scale: float = 1.0,
                  above=None, below=None, min_change=None, source: str = "", transforms: str = "", which: str = "all") -> dict:
     """the JSON report of ``found`` (a ``MeshMeasurement``, or anything with its numbers): plain Python numbers, None where there is
@@ -130,16 +119,11 @@ def build_report(found, vertices, faces, frames, width, height, bounds, min_cos:
                          "usable_cameras": int(p.usable_cameras), "seen_vertices": int(found.seen), "tested_pairs": int(p.tested_pairs),
                          "accepted_pairs": int(p.accepted_pairs), "stack_limit_pairs": int(p.stack_limit_pairs)},
               "seen_share": float(found.seen_share), "mean_views": float(found.mean_views),
-              "residual": {"mean": _number(found.mean_difference), "rms": _number(found.rms_difference), "min": _number(found.min_difference),
-                           "max": _number(found.max_difference)},
-              "spread": {"mean": _number(found.mean_spread), "max": _number(found.max_spread)}}
+              "residual": {"mean": json_number(found.mean_difference), "rms": json_number(found.rms_difference), "min": json_number(found.min_difference),
+                           "max": json_number(found.max_difference)},
+              "spread": {"mean": json_number(found.mean_spread), "max": json_number(found.max_spread)}}
     if min_change is not None:
-        rows = _tool("mesh_compare").region_rows
-        report["min_change"] = float(min_change)
-        for name, regions, sign in (("model_above", above, True), ("model_below", below, False)):
-            report[name] = {"regions": rows(regions, sign, s), "area": float(regions.selected_area) * s * s,
-                            "share": float(regions.selected_area / regions.mesh_area) if regions.mesh_area > 0.0 else 0.0}
-        report["compared_area"] = float(above.mesh_area) * s * s
+        add_difference_regions(report, ("model_above", "model_below"), above, below, min_change, s)
     return report
 
 
@@ -154,13 +138,7 @@ def summary_line(report: dict) -> str:
 
 
 def region_lines(report: dict) -> list:
-    lines = []
-    for name in ("model_above", "model_below"):
-        for k, row in enumerate(report.get(name, {}).get("regions", [])):
-            c = row["centroid"]
-            lines.append(f"{name} {k}: area {row['area']:.6g}, {row['faces']} faces, mean {row['mean_difference']:+.2f} C, largest "
-                         f"{row['largest_change']:+.2f} C, centroid ({c[0]:.4g}, {c[1]:.4g}, {c[2]:.4g})")
-    return lines
+    return difference_region_lines(report, ("model_above", "model_below"))
 
 
 def main(argv=None) -> int:
@@ -172,19 +150,16 @@ def main(argv=None) -> int:
 
     meta = json.loads(args.transforms.read_text())
     index = select_frames(meta, args.frames)
-    view_tool = _tool("mesh_camera_view")
-    cameras = [view_tool.frame_camera(meta, k) for k in index]
+    cameras = [frame_camera(meta, k) for k in index]
     views = [CameraView(c["c2w"], c["fx"], c["fy"], c["cx"], c["cy"], c["width"], c["height"]) for c in cameras]
     width, height = views[0].width, views[0].height
     photos = load_photos(meta, index, args.transforms.parent, width, height)
-    dev = torch.device(args.device)
-    if dev.type != "cuda":
-        raise RuntimeError(f"--device {args.device}: thermo_nerf_amd projects photos only on a ROCm device (no CPU fallback exists)")
-    mesh, data = _tool("mesh_compare").load_mesh(args.mesh, dev)
+    dev = require_rocm_device(args.device, "projects photos")
+    mesh, data = load_mesh_ply(args.mesh, dev, with_bounds=False)
     if args.temperature_bounds is not None:
         bounds = (args.temperature_bounds[1], args.temperature_bounds[0])
     else:
-        bounds = view_tool._regions_tool().file_bounds(data["comments"])
+        bounds = file_bounds(data["comments"])
         if bounds is None:
             raise ValueError(f"{args.mesh} names no temperature_bounds: pass --temperature-bounds MAX MIN")
     found = mesh_measurement(mesh, build_mesh_bvh(mesh), views, torch.from_numpy(photos).to(dev), bounds, min_cos=args.min_cos,
@@ -204,9 +179,7 @@ def main(argv=None) -> int:
         write_mesh_ply(args.residual, found.residual)
         print(f"wrote {args.residual}")
     if args.report is not None:
-        args.report.parent.mkdir(parents=True, exist_ok=True)
-        args.report.write_text(json.dumps(report, indent=1) + "\n")
-        print(f"wrote {args.report}")
+        write_report(args.report, report)
     return 0
 
 

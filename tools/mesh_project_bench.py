@@ -16,21 +16,10 @@ gate.
 from __future__ import annotations
 
 import argparse
-import importlib.util
 import math
-import os
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-if ROOT not in sys.path:
-    sys.path.insert(0, ROOT)
-
-
-def _tool(name: str):
-    spec = importlib.util.spec_from_file_location(name, os.path.join(ROOT, "tools", name + ".py"))
-    module = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(module)
-    return module
+import mesh_scenes  # the sibling module: the scenes, event_ms, emit; it puts the repository on sys.path
 
 
 def ring_cameras(count: int, width: int, height: int, look_at):
@@ -105,14 +94,13 @@ def main() -> int:
 
     from thermo_nerf_amd.export import ThermalMesh, build_mesh_bvh, camera_records, project_images_into, vertex_normals
 
-    cast_bench = _tool("mesh_raycast_bench")
     dev = torch.device("cuda")
-    pos, temp, col, tri = cast_bench.room(args.cells, 1, dev)
+    pos, temp, col, tri = mesh_scenes.room(args.cells, 1, dev)
     mesh = ThermalMesh(pos, col, temp, None, tri)
     bvh = build_mesh_bvh(mesh)
     normals = vertex_normals(pos, tri)
     count, faces, k = int(pos.shape[0]), int(tri.shape[0]), args.cameras
-    records, width, height = camera_records(ring_cameras(k, args.width, args.height, cast_bench.look_at))
+    records, width, height = camera_records(ring_cameras(k, args.width, args.height, mesh_scenes.look_at))
     table = torch.from_numpy(records).to(dev)
     rotations = [torch.from_numpy(records[i, :12].reshape(3, 4)[:, :3].copy()).double().to(dev) for i in range(k)]
     gen = torch.Generator(device="cpu").manual_seed(11)
@@ -169,12 +157,7 @@ def main() -> int:
              f"{pairs / fa / 1e3:<15.1f} {pairs / fb / 1e3:.1f}",
              f"seen vertices {got[0]} of {count}; views differing between the two: {differ} of {count} vertices; largest |measured| difference "
              f"where the views agree: {worst:.3g} C"]
-    report = "\n".join(lines) + "\n"
-    print(report)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write(report)
+    mesh_scenes.emit(lines, args.out)
     return 0
 
 

@@ -13,89 +13,9 @@ calls, then ``--repeats`` timed calls each; median and range.  A record, not a g
 from __future__ import annotations
 
 import argparse
-import importlib.util
-import math
-import os
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-if ROOT not in sys.path:
-    sys.path.insert(0, ROOT)
-
-
-def _simplify_bench():
-    spec = importlib.util.spec_from_file_location("mesh_simplify_bench", os.path.join(ROOT, "tools", "mesh_simplify_bench.py"))
-    module = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(module)
-    return module
-
-
-def lattice_box(lo, hi, cells: int, inward: bool, jitter: float, gen):
-    """the six sides of an axis-aligned box as lattices of ``cells`` x ``cells`` two-triangle cells, the inner vertices of every side
-    moved by ``jitter`` of a cell inside its plane: (positions float64 [V, 3], triangles int64 [T, 3]) on the host"""
-    import torch
-
-    positions, triangles, base = [], [], 0
-    g = torch.linspace(0.0, 1.0, cells + 1, dtype=torch.float64)
-    ga, gb = torch.meshgrid(g, g, indexing="ij")
-    inner = ((ga > 0) & (ga < 1) & (gb > 0) & (gb < 1)).double()
-    i, j = torch.meshgrid(torch.arange(cells), torch.arange(cells), indexing="ij")
-    for axis in range(3):
-        for side in range(2):
-            a, b = (axis + 1) % 3, (axis + 2) % 3
-            shift = (torch.rand((2, cells + 1, cells + 1), generator=gen, dtype=torch.float64) - 0.5) * jitter / cells
-            p = torch.zeros((cells + 1, cells + 1, 3), dtype=torch.float64)
-            p[..., axis] = hi[axis] if side else lo[axis]
-            p[..., a] = lo[a] + (ga + inner * shift[0]) * (hi[a] - lo[a])
-            p[..., b] = lo[b] + (gb + inner * shift[1]) * (hi[b] - lo[b])
-            v00 = base + i * (cells + 1) + j
-            v10, v01, v11 = v00 + cells + 1, v00 + 1, v00 + cells + 2
-            quads = torch.stack([torch.stack([v00, v10, v11], -1), torch.stack([v00, v11, v01], -1)], -2).reshape(-1, 3)
-            if bool(side) == bool(inward):
-                quads = quads[:, [0, 2, 1]]
-            positions.append(p.reshape(-1, 3))
-            triangles.append(quads)
-            base += (cells + 1) ** 2
-    return torch.cat(positions), torch.cat(triangles)
-
-
-def room(cells: int, seed: int, dev):
-    """the room with five boxes in it, 12 cells^2 + 5 * 12 (cells / 4)^2 faces: (positions, temperature, colors, triangles)"""
-    import torch
-
-    gen = torch.Generator(device="cpu").manual_seed(seed)
-    parts = [lattice_box((0.0, 0.0, 0.0), (6.0, 4.0, 3.0), cells, True, 0.6, gen)]
-    for corner, size in (((0.5, 0.5, 0.0), (1.0, 0.8, 1.1)), ((2.2, 2.6, 0.0), (0.7, 0.9, 1.9)), ((3.6, 0.6, 0.0), (1.2, 1.2, 0.6)),
-                         ((0.6, 2.4, 0.0), (0.8, 1.0, 0.9)), ((4.6, 2.5, 0.0), (0.9, 0.9, 1.4))):
-        hi = tuple(c + s for c, s in zip(corner, size))
-        parts.append(lattice_box(corner, hi, max(cells // 4, 1), False, 0.6, gen))
-    positions, triangles, base = [], [], 0
-    for p, t in parts:
-        positions.append(p)
-        triangles.append(t + base)
-        base += p.shape[0]
-    pos = torch.cat(positions)
-    temp = 21.0 + 5.0 * torch.sin(pos[:, 0] * 1.7) * torch.cos(pos[:, 1] * 2.3) + 1.5 * pos[:, 2]
-    colors = (torch.rand((pos.shape[0], 3), generator=gen) * 255).to(torch.uint8)
-    return pos.float().to(dev), temp.float().to(dev), colors.to(dev), torch.cat(triangles).int().to(dev)
-
-
-def look_at(eye, target, up=(0.0, 0.0, 1.0)):
-    """3 x 4 camera-to-world rows in nerfstudio's convention (the camera looks along its -z, +y is up)"""
-    def sub(a, b):
-        return [x - y for x, y in zip(a, b)]
-
-    def cross(a, b):
-        return [a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0]]
-
-    def unit(a):
-        n = math.sqrt(sum(x * x for x in a))
-        return [x / n for x in a]
-
-    back = unit(sub(eye, target))
-    right = unit(cross(up, back))
-    true_up = cross(back, right)
-    return [[right[k], true_up[k], back[k], eye[k]] for k in range(3)]
+import mesh_scenes  # the sibling module: the scenes, event_ms, emit; it puts the repository on sys.path
 
 
 def main() -> int:
@@ -109,14 +29,14 @@ def main() -> int:
 
     import torch
 
-    from thermo_nerf_amd.export import (CameraView, MeshBVH, RasterView, ThermalMesh, camera_rays, mesh_bvh_bytes, mesh_bvh_workspace_bytes,
+    from thermo_nerf_amd.export import (MeshBVH, RasterView, ThermalMesh, camera_rays, mesh_bvh_bytes, mesh_bvh_workspace_bytes,
                                         build_mesh_bvh, mesh_raycast_into, mesh_rasterize_into, mesh_rasterize_workspace_bytes)
 
-    event_ms = _simplify_bench().event_ms
+    event_ms, cell = mesh_scenes.event_ms, mesh_scenes.cell
     dev = torch.device("cuda")
     w, h = args.width, args.height
     n = w * h
-    camera = CameraView(look_at((5.4, 3.5, 2.3), (1.6, 1.2, 0.5)), 0.8 * w, 0.8 * w, w / 2.0, h / 2.0, w, h)
+    camera = mesh_scenes.room_camera(w, h)
     origins, directions = camera_rays(camera, dev)
     face = torch.empty((n,), dtype=torch.int32, device=dev)
     t, temperature = torch.empty((n,), device=dev), torch.empty((n,), device=dev)
@@ -129,7 +49,7 @@ def main() -> int:
              "rasterise ms (same mesh, same pixel count, orthographic)"]
     cast_ms = []
     for cells in args.cells:
-        pos, temp, col, tri = room(cells, 1, dev)
+        pos, temp, col, tri = mesh_scenes.room(cells, 1, dev)
         mesh = ThermalMesh(pos, col, temp, None, tri)
         faces = int(tri.shape[0])
         blob = torch.empty((mesh_bvh_bytes(faces),), dtype=torch.uint8, device=dev)
@@ -149,9 +69,6 @@ def main() -> int:
                                                       workspace=rws), args.repeats)
         cast_ms.append((faces, closest[0]))
 
-        def cell(ms):
-            return f"{ms[0]:8.4f} ({ms[1]:.4f} .. {ms[2]:.4f})"
-
         lines.append(f"{faces:<10d} {depth:<7d} {got[0] / n:<11.4f} {cell(build):<29s} {cell(closest):<30s} {n / closest[0] / 1e3:<9.1f} "
                      f"{cell(any_hit):<30s} {cell(raster)}")
         if got[3] != 0:
@@ -160,12 +77,7 @@ def main() -> int:
     if len(cast_ms) > 1:
         (f0, m0), (f1, m1) = cast_ms[0], cast_ms[-1]
         lines.append(f"closest-hit cast at {f1} faces / at {f0} faces = {m1 / m0:.2f} x for {f1 / f0:.2f} x the faces (medians above)")
-    report = "\n".join(lines) + "\n"
-    print(report)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write(report)
+    mesh_scenes.emit(lines, args.out)
     return 0
 
 

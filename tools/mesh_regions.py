@@ -16,7 +16,6 @@ as a mesh: ``--colors rgb`` keeps the file's colours, ``thermal`` maps the tempe
 from __future__ import annotations
 
 import argparse
-import json
 import math
 import os
 import sys
@@ -25,6 +24,9 @@ from pathlib import Path
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
+
+from thermo_nerf_amd.export.cli import (file_bounds, json_number, load_mesh_ply, require_rocm_device, thermal_bytes,  # noqa: E402,F401
+                                        write_report)
 
 
 def parse(argv=None) -> argparse.Namespace:
@@ -53,10 +55,6 @@ def parse(argv=None) -> argparse.Namespace:
     return args
 
 
-def _bound(x: float):
-    return None if math.isinf(x) else float(x)
-
-
 def build_report(found, positions, temperature, num_faces: int, length_scale: float = 1.0, source: str = "") -> dict:
     """the JSON report of ``found`` (a ``ThermalRegions``) over the host arrays ``positions`` [V,3] and ``temperature`` [V] of its
     mesh: plain Python numbers; lengths times ``length_scale``, areas times its square"""
@@ -78,7 +76,7 @@ def build_report(found, positions, temperature, num_faces: int, length_scale: fl
                      "hottest_vertex": vertex(row["hottest_vertex"]), "coldest_vertex": vertex(row["coldest_vertex"])})
     mesh_area, selected_area = float(found.mesh_area) * s2, float(found.selected_area) * s2
     return {"mesh": source, "length_scale": s,
-            "window": {"min_temperature": _bound(found.window[0]), "max_temperature": _bound(found.window[1])},
+            "window": {"min_temperature": json_number(found.window[0], keep_nan=True), "max_temperature": json_number(found.window[1], keep_nan=True)},
             "counts": {"vertices": int(len(positions)), "faces": int(num_faces), "usable_faces": int(found.usable_faces),
                        "selected_faces": int(found.selected_faces), "regions": int(found.num_regions), "reported_regions": len(rows)},
             "mesh_area": mesh_area, "selected_area": selected_area,
@@ -95,44 +93,14 @@ def region_lines(report: dict) -> list:
     return lines
 
 
-def thermal_bytes(temperature, bounds):
-    """uint8 [M,3]: the magma table at trunc(256 (t - lo) / (hi - lo)), clamped to the table"""
-    import numpy as np
-
-    from thermo_nerf_amd import colormaps
-
-    t = np.asarray(temperature, np.float64)
-    lo, hi = bounds if bounds is not None else ((float(t.min()), float(t.max())) if len(t) else (0.0, 1.0))
-    x = (t - lo) / (hi - lo) if hi > lo else np.zeros_like(t)
-    index = np.clip(np.nan_to_num(np.trunc(x * 256.0), nan=0.0, posinf=255.0, neginf=0.0), 0, 255).astype(np.int64)
-    return colormaps.table_u8("magma")[index]
-
-
-def file_bounds(comments):
-    """the (lo, hi) of the file's ``temperature_bounds`` comment, or None"""
-    for line in comments:
-        parts = line.split()
-        if len(parts) == 3 and parts[0] == "temperature_bounds" and parts[1] != "none":
-            return float(parts[1]), float(parts[2])
-    return None
-
-
 def main(argv=None) -> int:
     args = parse(argv)
 
     import torch
 
-    from thermo_nerf_amd.export import ThermalMesh, read_mesh_ply, regions_mesh, thermal_regions, write_mesh_ply
+    from thermo_nerf_amd.export import regions_mesh, thermal_regions, write_mesh_ply
 
-    data = read_mesh_ply(args.mesh)
-    dev = torch.device(args.device)
-    if dev.type != "cuda":
-        raise RuntimeError(f"--device {args.device}: thermo_nerf_amd analyses meshes only on a ROCm device (no CPU fallback exists)")
-    bounds = file_bounds(data["comments"])
-    normals = data.get("normals")
-    mesh = ThermalMesh(torch.from_numpy(data["positions"].copy()).to(dev), torch.from_numpy(data["colors"].copy()).to(dev),
-                       torch.from_numpy(data["temperature"].copy()).to(dev), None, torch.from_numpy(data["triangles"].copy()).to(dev),
-                       bounds, None if normals is None else torch.from_numpy(normals.copy()).to(dev))
+    mesh, data = load_mesh_ply(args.mesh, require_rocm_device(args.device, "analyses meshes"), with_bounds=True)
     found = thermal_regions(mesh, args.min_temperature, args.max_temperature, min_area=args.min_area, top=args.top)
     report = build_report(found, data["positions"], data["temperature"], len(data["triangles"]), args.length_scale, str(args.mesh))
     share = 100.0 * report["selected_share"]
@@ -141,13 +109,11 @@ def main(argv=None) -> int:
           f"{report['counts']['regions']} regions, {report['counts']['reported_regions']} reported")
     for line in region_lines(report):
         print(line)
-    args.report.parent.mkdir(parents=True, exist_ok=True)
-    args.report.write_text(json.dumps(report, indent=1) + "\n")
-    print(f"wrote {args.report}")
+    write_report(args.report, report)
     if args.output is not None:
         part = regions_mesh(mesh, found)
         if args.colors == "thermal":
-            part.thermal_colors = torch.from_numpy(thermal_bytes(part.temperature.cpu().numpy(), bounds))
+            part.thermal_colors = torch.from_numpy(thermal_bytes(part.temperature.cpu().numpy(), mesh.temperature_bounds))
         write_mesh_ply(args.output, part, colors=args.colors)
         print(f"wrote {args.output}: vertices {len(part)}, triangles {int(part.triangles.shape[0])}")
     return 0

@@ -15,21 +15,10 @@ the table — with device events around the call; the raw ``tn_mesh_regions`` en
 from __future__ import annotations
 
 import argparse
-import importlib.util
 import math
-import os
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-if ROOT not in sys.path:
-    sys.path.insert(0, ROOT)
-
-
-def _simplify_bench():
-    spec = importlib.util.spec_from_file_location("mesh_simplify_bench", os.path.join(ROOT, "tools", "mesh_simplify_bench.py"))
-    module = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(module)
-    return module
+import mesh_scenes  # the sibling module: the scenes, event_ms, emit; it puts the repository on sys.path
 
 
 def main() -> int:
@@ -46,10 +35,9 @@ def main() -> int:
                                         mesh_workspace_bytes, thermal_regions)
     from thermo_nerf_amd.export.regions import REGION_BYTES, max_regions
 
-    sphere = _simplify_bench()
     dev = torch.device("cuda")
     n = args.resolution
-    volume, params, _ = sphere.sphere_volume(n, dev)
+    volume, params, _ = mesh_scenes.sphere_volume(n, dev)
     counts = torch.zeros((2,), dtype=torch.int64, device=dev)
     ws = torch.empty((mesh_workspace_bytes((n,) * 3),), dtype=torch.uint8, device=dev)
     mesh_extract(volume, params, counts=counts, workspace=ws)
@@ -59,7 +47,7 @@ def main() -> int:
     mesh_extract(volume, params, counts=counts, positions=mesh.positions, colors=mesh.colors, temperature=mesh.temperature,
                  triangles=mesh.triangles, workspace=ws)
     del volume, ws
-    p = mesh.positions * (args.cells * math.pi / (2 * sphere.HALF))
+    p = mesh.positions * (args.cells * math.pi / (2 * mesh_scenes.HALF))
     checker = torch.where(torch.sin(p[:, 0]) * torch.sin(p[:, 1]) * torch.sin(p[:, 2]) > 0, 30.0, 15.0).to(torch.float32)
     fields = (("one region of the whole surface", mesh.temperature, (-math.inf, math.inf)),
               (f"checkerboard of {args.cells:g} cells, the warm ones", checker, (26.0, math.inf)))
@@ -69,11 +57,11 @@ def main() -> int:
     rows = torch.empty((cap * REGION_BYTES,), dtype=torch.uint8, device=dev)
     face_region = torch.empty((t,), dtype=torch.int32, device=dev)
     rws = torch.empty((mesh_regions_workspace_bytes(v, t),), dtype=torch.uint8, device=dev)
-    lines = [f"thermal regions of the surface-nets mesh of an analytic sphere (radius {sphere.RADIUS}, {n}^3 volume over "
-             f"[-{sphere.HALF}, {sphere.HALF}]^3): {v} vertices, {t} triangles; workspace {rws.numel() / 2 ** 20:.1f} MiB; device events "
+    lines = [f"thermal regions of the surface-nets mesh of an analytic sphere (radius {mesh_scenes.RADIUS}, {n}^3 volume over "
+             f"[-{mesh_scenes.HALF}, {mesh_scenes.HALF}]^3): {v} vertices, {t} triangles; workspace {rws.numel() / 2 ** 20:.1f} MiB; device events "
              f"around each call, 3 warm-up calls, {args.repeats} timed calls, ms per call",
              "what                                                                      regions    selected  largest region   median ms   min .. max"]
-    c = sphere.event_ms(lambda: mesh_components(mesh.triangles, v), args.repeats)
+    c = mesh_scenes.event_ms(lambda: mesh_components(mesh.triangles, v), args.repeats)
     lines.append(f"{'tn_mesh_components of all triangles (the yardstick)':72s} {'-':>8s} {'-':>11s} {'-':>15s} {c[0]:11.4f}   {c[1]:.4f} .. {c[2]:.4f}")
     for name, temperature, window in fields:
         field = ThermalMesh(mesh.positions, mesh.colors, temperature, None, mesh.triangles, mesh.temperature_bounds)
@@ -85,14 +73,9 @@ def main() -> int:
             mesh_regions_into(field, *window, counts=three, totals=two, face_region=face_region, regions=rows, workspace=rws)
 
         for what, fn in ((f"tn_mesh_regions alone, {name}", raw_call), (f"thermal_regions, {name}", lambda: thermal_regions(field, *window))):
-            m = sphere.event_ms(fn, args.repeats)
+            m = mesh_scenes.event_ms(fn, args.repeats)
             lines.append(f"{what:72s} {tail} {m[0]:11.4f}   {m[1]:.4f} .. {m[2]:.4f}")
-    report = "\n".join(lines) + "\n"
-    print(report)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write(report)
+    mesh_scenes.emit(lines, args.out)
     return 0
 
 

@@ -20,8 +20,6 @@ vertices down.  ``--output`` gets the moving mesh in the fixed mesh's frame, whi
 from __future__ import annotations
 
 import argparse
-import importlib.util
-import json
 import math
 import os
 import sys
@@ -31,13 +29,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
-
-def _tool(name: str):
-    """another command line of tools/: the helpers shared with it"""
-    spec = importlib.util.spec_from_file_location(f"{name}_tool", os.path.join(ROOT, "tools", f"{name}.py"))
-    module = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(module)
-    return module
+from thermo_nerf_amd.export.cli import json_number, load_mesh_ply, require_rocm_device, write_report  # noqa: E402
 
 
 def parse(argv=None) -> argparse.Namespace:
@@ -64,11 +56,6 @@ def parse(argv=None) -> argparse.Namespace:
     if args.max_points is not None and args.max_points < 1:
         ap.error("--max-points must be >= 1")
     return args
-
-
-def _number(x):
-    """a float for JSON: None for what JSON cannot say (NaN, the infinities, an absent value)"""
-    return None if x is None or not math.isfinite(float(x)) else float(x)
 
 
 def starting_matrix(initial, pairs, with_scale: bool):
@@ -99,9 +86,9 @@ def build_report(found, vertices: int, points: int, source: str = "", reference:
             "points": int(points), "status": found.status, "iterations": int(found.iterations), "scale": float(found.scale),
             "matrix": [[float(x) for x in row] for row in found.matrix], "start": None if start is None else [[float(x) for x in row] for row in start],
             "matched": int(found.matched), "matched_share": float(found.matched_share), "usable_points": int(found.usable_points),
-            "rms": [_number(x) for x in found.rms],
-            "stages": [{"max_distance": _number(s["max_distance"]), "status": s["status"], "iterations": int(s["iterations"]),
-                        "matched": int(s["matched"]), "matched_share": float(s["matched_share"]), "rms": _number(s["rms"])} for s in found.stages]}
+            "rms": [json_number(x) for x in found.rms],
+            "stages": [{"max_distance": json_number(s["max_distance"]), "status": s["status"], "iterations": int(s["iterations"]),
+                        "matched": int(s["matched"]), "matched_share": float(s["matched_share"]), "rms": json_number(s["rms"])} for s in found.stages]}
 
 
 def summary_line(report: dict) -> str:
@@ -115,26 +102,21 @@ def main(argv=None) -> int:
     args = parse(argv)
 
     import numpy as np
-    import torch
 
     from thermo_nerf_amd.export import build_mesh_bvh, register_mesh, transform_mesh, write_mesh_ply
 
-    load_mesh = _tool("mesh_compare").load_mesh
-    dev = torch.device(args.device)
-    if dev.type != "cuda":
-        raise RuntimeError(f"--device {args.device}: thermo_nerf_amd registers meshes only on a ROCm device (no CPU fallback exists)")
-    moving, data = load_mesh(args.moving, dev)
-    fixed, _ = load_mesh(args.fixed, dev)
+    dev = require_rocm_device(args.device, "registers meshes")
+    moving, data = load_mesh_ply(args.moving, dev, with_bounds=False)
+    fixed, _ = load_mesh_ply(args.fixed, dev, with_bounds=False)
     start = starting_matrix(args.initial, args.pairs, args.with_scale)
     found = register_mesh(moving, build_mesh_bvh(fixed), max_points=args.max_points, initial=start, max_distance=list(args.max_distance),
                           metric=args.metric, with_scale=args.with_scale, iterations=args.iterations)
     points = len(data["positions"]) if args.max_points is None else len(range(0, len(data["positions"]), -(-len(data["positions"]) // args.max_points)))
     report = build_report(found, len(data["positions"]), points, str(args.moving), str(args.fixed), args.metric, args.with_scale, start)
     print(summary_line(report))
-    for path in (args.report, args.matrix, args.output):
+    for path in (args.matrix, args.output):
         path.parent.mkdir(parents=True, exist_ok=True)
-    args.report.write_text(json.dumps(report, indent=1) + "\n")
-    print(f"wrote {args.report}")
+    write_report(args.report, report)
     np.savetxt(args.matrix, found.matrix, fmt="%.17g")
     print(f"wrote {args.matrix}")
     if found.status in ("too_few", "degenerate"):

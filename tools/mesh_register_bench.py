@@ -18,20 +18,9 @@ record, not a gate.
 from __future__ import annotations
 
 import argparse
-import importlib.util
-import os
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-if ROOT not in sys.path:
-    sys.path.insert(0, ROOT)
-
-
-def _tool(name: str):
-    spec = importlib.util.spec_from_file_location(name, os.path.join(ROOT, "tools", name + ".py"))
-    module = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(module)
-    return module
+import mesh_scenes  # the sibling module: the scenes, event_ms, emit; it puts the repository on sys.path
 
 
 def small_similarity(center):
@@ -74,8 +63,7 @@ def main() -> int:
 
     from thermo_nerf_amd.export import (ThermalMesh, build_mesh_bvh, mesh_closest_into, register_points_into, register_workspace_bytes)
 
-    cast_bench = _tool("mesh_raycast_bench")
-    event_ms = _tool("mesh_simplify_bench").event_ms
+    event_ms = mesh_scenes.event_ms
     dev = torch.device("cuda")
     k, damping, radius = args.iterations, 1e-6, 0.25
     lines = [f"tn_mesh_register on the room of mesh_raycast_bench, the cloud its own vertices under a small similarity (0.02 rad, 1 % "
@@ -86,7 +74,7 @@ def main() -> int:
              f"faces      points    fused, 1 iteration ms           fused, {k} iterations: ms / iteration   (a) closest ms                  "
              f"(b) composed iteration ms       fused / (a)   (b) / fused   matched   |fused - composed| after 1"]
     for cells in args.cells:
-        pos, temp, col, tri = cast_bench.room(cells, 1, dev)
+        pos, temp, col, tri = mesh_scenes.room(cells, 1, dev)
         mesh = ThermalMesh(pos, col, temp, None, tri)
         faces, n = int(tri.shape[0]), int(pos.shape[0])
         bvh = build_mesh_bvh(mesh)
@@ -150,12 +138,7 @@ def main() -> int:
                      f"{one[0] / floor[0]:<13.2f} {split[0] / (many[0] / k):<13.2f} {matched:<9d} {apart:.3g}")
         lines.append(f"           after {k} fused iterations: max |entry| of the transform minus the known similarity {error:.3g}")
         del bvh
-    report = "\n".join(lines) + "\n"
-    print(report)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write(report)
+    mesh_scenes.emit(lines, args.out)
     return 0
 
 

@@ -12,50 +12,10 @@ host reads — with device events around the call; the raw ``tn_mesh_simplify`` 
 from __future__ import annotations
 
 import argparse
-import os
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-if ROOT not in sys.path:
-    sys.path.insert(0, ROOT)
-RADIUS, HALF, TRUNCATION_STEPS = 0.3, 0.5, 4.0
-
-
-def sphere_volume(n: int, dev):
-    """(volume [7, n, n, n], params): tsdf = clamp((|p| - RADIUS) / truncation, -1, 1) with weight 1, thermal (z / RADIUS + 1) / 2"""
-    import torch
-
-    from thermo_nerf_amd.export import mesh_params
-
-    step = 2 * HALF / (n - 1)
-    truncation = TRUNCATION_STEPS * step
-    g = torch.linspace(-HALF, HALF, n, device=dev)
-    z, y, x = torch.meshgrid(g, g, g, indexing="ij")
-    volume = torch.zeros((7, n, n, n), dtype=torch.float32, device=dev)
-    volume[0] = (((x * x + y * y + z * z).sqrt() - RADIUS) / truncation).clamp(-1.0, 1.0)
-    volume[1] = 1.0
-    volume[2] = ((z / RADIUS + 1.0) / 2.0).clamp(0.0, 1.0)
-    volume[3], volume[4], volume[5], volume[6] = 0.25, 0.5, 0.75, 1.0
-    return volume, mesh_params((-HALF,) * 3, (HALF,) * 3, (n,) * 3, truncation, max_temperature=33.0, min_temperature=14.0), step
-
-
-def event_ms(fn, repeats: int):
-    """(median, min, max) ms of ``repeats`` calls, each between two device events, after 3 warm-up calls"""
-    import torch
-
-    for _ in range(3):
-        fn()
-    torch.cuda.synchronize()
-    times = []
-    for _ in range(repeats):
-        start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        start.record()
-        fn()
-        stop.record()
-        stop.synchronize()
-        times.append(start.elapsed_time(stop))
-    times.sort()
-    return times[len(times) // 2], times[0], times[-1]
+import mesh_scenes  # the sibling module: the scenes, event_ms, emit; it puts the repository on sys.path
+from mesh_scenes import HALF, RADIUS, TRUNCATION_STEPS, event_ms, sphere_volume
 
 
 def main() -> int:
@@ -109,12 +69,7 @@ def main() -> int:
                          (f"tn_mesh_simplify alone, cell {steps:g} steps", lambda: mesh_simplify_into(mesh, grid, counts=four, workspace=sws, **out))):
             m = event_ms(fn, args.repeats)
             lines.append(f"{name:44s} {v:9d} {t:11d}   {tail} {m[0]:11.4f}   {m[1]:.4f} .. {m[2]:.4f}")
-    report = "\n".join(lines) + "\n"
-    print(report)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write(report)
+    mesh_scenes.emit(lines, args.out)
     return 0
 
 

@@ -20,8 +20,6 @@ and its areas by L^2, as in ``tools/mesh_regions.py``.  One summary line is prin
 from __future__ import annotations
 
 import argparse
-import importlib.util
-import json
 import math
 import os
 import sys
@@ -31,17 +29,11 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
+from thermo_nerf_amd.export.cli import json_number, load_mesh_ply, require_rocm_device, write_report  # noqa: E402
+
 # --view: (forward, up)
 VIEWS = {"+x": ((1, 0, 0), (0, 0, 1)), "-x": ((-1, 0, 0), (0, 0, 1)), "+y": ((0, 1, 0), (0, 0, 1)), "-y": ((0, -1, 0), (0, 0, 1)),
          "+z": ((0, 0, 1), (0, 1, 0)), "-z": ((0, 0, -1), (0, 1, 0))}
-
-
-def _regions_tool():
-    """tools/mesh_regions.py: the helpers shared with it (``file_bounds``)"""
-    spec = importlib.util.spec_from_file_location("mesh_regions_tool", os.path.join(ROOT, "tools", "mesh_regions.py"))
-    module = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(module)
-    return module
 
 
 def parse(argv=None) -> argparse.Namespace:
@@ -88,10 +80,6 @@ def parse(argv=None) -> argparse.Namespace:
     return args
 
 
-def _bound(x: float):
-    return None if math.isinf(x) or math.isnan(x) else float(x)
-
-
 def build_report(found, temperature, face, depth, num_vertices: int, num_faces: int, length_scale: float = 1.0, source: str = "") -> dict:
     """the JSON report of ``found`` (a ``Thermogram``) over the host arrays ``temperature``, ``face`` and ``depth`` [H, W] of its
     images: plain Python numbers; lengths times ``length_scale``, areas times its square.  The hottest / coldest pixel is the first
@@ -117,14 +105,14 @@ def build_report(found, temperature, face, depth, num_vertices: int, num_faces: 
             "view": {"origin": [float(c) * s for c in view.origin], "right": [float(c) for c in view.right],
                      "down": [float(c) for c in view.down], "forward": [float(c) for c in view.forward],
                      "pixel_size": float(view.pixel_size) * s, "width": int(view.width), "height": int(view.height),
-                     "near": None if _bound(view.near) is None else view.near * s, "far": None if _bound(view.far) is None else view.far * s,
+                     "near": None if json_number(view.near) is None else view.near * s, "far": None if json_number(view.far) is None else view.far * s,
                      "cull_back": bool(view.cull)},
             "counts": {"vertices": int(num_vertices), "faces": int(num_faces), "usable_faces": int(found.usable_faces),
                        "drawn_faces": int(found.drawn_faces), "pixels": int(view.width) * int(view.height),
                        "covered_pixels": int(found.covered)},
             "covered_area": float(found.covered_area) * s2,
-            "mean_temperature": _bound(found.mean_temperature), "min_temperature": _bound(found.min_temperature),
-            "max_temperature": _bound(found.max_temperature), "hottest_pixel": hottest, "coldest_pixel": coldest}
+            "mean_temperature": json_number(found.mean_temperature), "min_temperature": json_number(found.min_temperature),
+            "max_temperature": json_number(found.max_temperature), "hottest_pixel": hottest, "coldest_pixel": coldest}
 
 
 def summary_line(report: dict, source) -> str:
@@ -140,18 +128,11 @@ def main(argv=None) -> int:
     args = parse(argv)
 
     import numpy as np
-    import torch
     from PIL import Image
 
-    from thermo_nerf_amd.export import ThermalMesh, fit_view, mesh_thermogram, read_mesh_ply
+    from thermo_nerf_amd.export import fit_view, mesh_thermogram
 
-    data = read_mesh_ply(args.mesh)
-    dev = torch.device(args.device)
-    if dev.type != "cuda":
-        raise RuntimeError(f"--device {args.device}: thermo_nerf_amd rasterises meshes only on a ROCm device (no CPU fallback exists)")
-    bounds = _regions_tool().file_bounds(data["comments"])
-    mesh = ThermalMesh(torch.from_numpy(data["positions"].copy()).to(dev), torch.from_numpy(data["colors"].copy()).to(dev),
-                       torch.from_numpy(data["temperature"].copy()).to(dev), None, torch.from_numpy(data["triangles"].copy()).to(dev), bounds)
+    mesh, data = load_mesh_ply(args.mesh, require_rocm_device(args.device, "rasterises meshes"), with_bounds=True)
     view = fit_view(mesh.positions, args.forward, args.up, pixel_size=args.pixel_size, width=args.width, near=args.near, far=args.far,
                     cull=args.cull_back)
     found = mesh_thermogram(mesh, view)
@@ -167,8 +148,7 @@ def main(argv=None) -> int:
         with open(args.temperatures, "wb") as f:  # (np.save given a name would append .npy to one without it)
             np.save(f, temperature)
     if args.report is not None:
-        args.report.parent.mkdir(parents=True, exist_ok=True)
-        args.report.write_text(json.dumps(report, indent=1) + "\n")
+        write_report(args.report, report, say=False)
     return 0
 
 

@@ -17,21 +17,10 @@ A record, not a gate.
 from __future__ import annotations
 
 import argparse
-import importlib.util
 import math
-import os
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-if ROOT not in sys.path:
-    sys.path.insert(0, ROOT)
-
-
-def _simplify_bench():
-    spec = importlib.util.spec_from_file_location("mesh_simplify_bench", os.path.join(ROOT, "tools", "mesh_simplify_bench.py"))
-    module = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(module)
-    return module
+import mesh_scenes  # the sibling module: the scenes, event_ms, emit; it puts the repository on sys.path
 
 
 def sheet(n: int, side: int, depth: float, seed: int, dev):
@@ -82,7 +71,7 @@ def main() -> int:
     from thermo_nerf_amd.export import (RasterView, ThermalMesh, mesh_raster_small_box, mesh_rasterize_into,
                                         mesh_rasterize_workspace_bytes)
 
-    event_ms = _simplify_bench().event_ms
+    event_ms = mesh_scenes.event_ms
     dev = torch.device("cuda")
     side = args.side
     pixels = side * side
@@ -136,12 +125,7 @@ def main() -> int:
     swept = run("(b) 1000 faces of ~10^4 pixels, swept in tiles (as built)", big)
     alone = run("(b) the same, every face by its own thread (threshold 16384)", big, small_box=16384)
     lines.append(f"(b) one thread per face / swept in tiles = {alone[0] / swept[0]:.1f} x (ranges above)")
-    report = "\n".join(lines) + "\n"
-    print(report)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write(report)
+    mesh_scenes.emit(lines, args.out)
     return 0
 
 
