@@ -1164,6 +1164,107 @@ int tn_mesh_register(const float *positions, const float *temperature, const int
                      const tn_register_params *params, double *transform, double *history, int64_t *result, void *workspace,
                      size_t workspace_bytes, void *stream);
 
+/* Half-edge twins of an indexed triangle list: face adjacency across edges, and whether the mesh is closed, manifold and consistently
+ * oriented.  triangles [T, 3] int32, V = num_vertices, T = num_triangles.  Every output is defined to the bit.
+ *   half-edge h = 3 f + j runs from tri[f][j] to tri[f][(j + 1) % 3].
+ *   STRUCTURAL   a face whose three indices lie in [0, V) and are distinct.
+ *   edge class   the half-edges of structural faces with the same unordered vertex pair.
+ *   twin (int32 [3T], always fully written): the other half-edge of a class that has exactly two members running in opposite
+ *               directions; -1 for every other half-edge, the three half-edges of a non-structural face included.
+ *   counts (device int64 [4], OVERWRITTEN): [0] the classes (edges), [1] the classes of one member (boundary edges), [2] the classes of
+ *               three or more members (non-manifold edges), [3] the classes of two members that run in the same direction
+ *               (inconsistent orientation).  A closed, manifold, consistently oriented mesh has [1] = [2] = [3] = 0.
+ * How: one uint64 key lo * V + hi per half-edge (V * V for a non-structural face: above every class), key_bits = the bit length of
+ * V * V; the stable device sort of the pairs (key, h); one thread per sorted position: the head of a class looks at its next two
+ * neighbours, writes the twins and counts (one integer atomic per block and count).  Nothing in the outputs depends on the order inside
+ * a class.  workspace: tn_mesh_half_edges_workspace_bytes(V, T) device bytes, 8-byte aligned; 0 for counts out of range.  Launches on
+ * `stream` only: no allocation, no host synchronisation, no float atomics, no block waits for another.
+ * TN_ERR_NULL: counts is NULL; triangles, twin or the workspace with T > 0; TN_ERR_SHAPE: V < 0 or > 2^31 - 1, T < 0 or 3T > 2^31 - 1,
+ * triangles / twin not 4-byte aligned, counts / workspace not 8-byte aligned; TN_ERR_WORKSPACE: workspace_bytes too small (with T > 0).
+ * All are returned before any launch.  T == 0: TN_OK, counts are zeroed, nothing else is written. */
+size_t tn_mesh_half_edges_workspace_bytes(int64_t num_vertices, int64_t num_triangles);
+int tn_mesh_half_edges(const int32_t *triangles, int64_t num_triangles, int64_t num_vertices, int32_t *twin, int64_t *counts,
+                       void *workspace, size_t workspace_bytes, void *stream);
+
+/* Level-set curves of a per-vertex scalar on an indexed triangle list, chained into ordered polylines: isotherms (the scalar is the
+ * temperature itself) and plane sections (the scalar is the signed distance to a plane).  positions [V, 3] floats, temperature [V]
+ * floats, triangles [T, 3] int32, twin [3T] int32 as tn_mesh_half_edges writes it, V = num_vertices, T = num_triangles.  `params` is a
+ * HOST struct, read before the call returns: 1 <= num_levels = K <= 256 levels, finite and strictly ascending, and the plane's normal.
+ * `scalar` is NULL for plane mode or a device float [V] for scalar mode (isotherms pass the temperature array itself).  Every output is
+ * defined to the bit.  add / sub / mul / div / sqrt below are single correctly rounded fp64 operations, nothing is contracted; (double)
+ * of a float is exact, (float) of a double rounds to nearest even.
+ *   scalar s_v   scalar mode: (double)scalar[v]; plane mode: add(add(mul(nx, px), mul(ny, py)), mul(nz, pz)) with the position widened
+ *                to double.
+ *   USABLE       a structural face (see tn_mesh_half_edges) with all nine coordinates, all three temperatures and all three scalars
+ *                finite (a plane scalar is finite unless the normal is beyond 1e269).
+ *   HIGH         vertex v at level L when s_v >= L, compared in fp64.  A usable face with scalar minimum m and maximum M carries one
+ *                segment for every level k with m < L_k <= M: the levels first_f .. last_f - 1, first = #{L <= m}, last = #{L <= M}.  A
+ *                vertex exactly on a level is HIGH, so every crossing lies on exactly two edges of the face (curves through vertices
+ *                stay consistent, possibly with segments of length zero).
+ *   numbering    face-major: seg = base_f + (k - first_f), base_f the exclusive prefix of the faces' segment counts in ascending face
+ *                index; S is the total.
+ *   direction    rotate the corners so that c0 is the corner whose class differs from the other two; the crossed half-edges are
+ *                hA = c0 -> c1 and hB = c2 -> c0.  With c0 HIGH the segment starts on hA and ends on hB, otherwise it starts on hB and
+ *                ends on hA: the high side lies on the left, seen against the face's orientation.
+ *   crossing     of half-edge h between vertices a and b at level L, lo the vertex that is not HIGH and hi the HIGH one:
+ *                w = div(sub(L, s_lo), sub(s_hi, s_lo)); position per axis (float)add(p_lo, mul(w, sub(p_hi, p_lo))); temperature
+ *                (float)add(t_lo, mul(w, sub(t_hi, t_lo))).  It depends on (lo, hi, L) only: both faces of an edge compute the same bits.
+ *   successor    g = twin[the end half-edge]; none when g is outside [0, 3T), face g / 3 is not usable or does not carry level k;
+ *                otherwise segment base_{g/3} + (k - first_{g/3}).  The predecessor of a segment is the segment it succeeds.  With a twin
+ *                table of this mesh in- and out-degree are at most 1: the segments form paths and cycles.
+ *   curves       a path is an OPEN curve and starts at its head (the segment without a predecessor); a cycle is a CLOSED curve and starts
+ *                at its lowest-numbered segment.  Curves are numbered q = 0 .. Q-1 in ascending number of their first segment.  A curve
+ *                of n segments has n + 1 points: the start of its first segment, then the end of every segment in order (a closed curve
+ *                repeats its first point bit for bit).  Its points begin at first_point = (the segments of earlier curves) + q;
+ *                P = S + Q.
+ *   per point    point_positions [P, 3], point_temperature [P]; point_face: the face of the segment that starts there, for the last
+ *                point of a curve the face of the last segment; point_arc: +0.0 at first_point, arc[j+1] = add(arc[j], len_j),
+ *                len_j = sqrt(add(add(mul(dx, dx), mul(dy, dy)), mul(dz, dz))), d the per-axis sub of the rounded fp32 points j + 1 and
+ *                j in fp64: a sequential sum in point order.
+ *   tn_mesh_curve, row q of `curves` (40 bytes):
+ *     length            arc of the last point
+ *     level             k;  first_point, points = n + 1;  closed 0 or 1;  first_face: the face of the first segment
+ *     mean_temperature  (float)div(W, length), W accumulated from +0.0 in point order, W = add(W, mul(len_j, mul(0.5, add(t_j, t_j+1))))
+ *                       with t the fp32 point temperatures widened to double; with length == 0 the NaN 0x7fc00000
+ *     min_temperature, max_temperature   over the curve's points, in the numbers' order with -0.0 below +0.0
+ *   counts (device int64 [5], OVERWRITTEN): [0] S, the FULL number of segments, [1] Q, [2] P, [3] the closed curves, [4] the usable
+ *                faces.  With S > capacity_segments (0: the sizing call, in which every output pointer but counts may be NULL) [1], [2]
+ *                and [3] are 0 and no output array is written; the kernels decide that on the device.  Otherwise the point arrays need
+ *                room for 2 * capacity_segments rows and curves for capacity_segments rows.
+ * How: count per face by binary search over the levels, one-block scan, emit the segments with their successors; the predecessors by
+ * one scatter; list ranking by pointer jumping over ping-pong arrays, ceil(log2(max(2, capacity_segments))) launches per sweep, each
+ * reading one array and writing the other: a first sweep carries (ancestor, lowest segment seen) and finds every path's head and every
+ * cycle's lowest member, the cycles are cut there, a second sweep yields the ranks; the last segment of a curve writes the curve's
+ * segment count to its first segment; count / scan / emit over the first segments numbers and places the curves; every segment writes
+ * its points to first_point + rank; one wave per curve adds 64 lengths at a time lane by lane.  workspace:
+ * tn_mesh_isolines_workspace_bytes(V, T, capacity_segments) device bytes, 8-byte aligned; 0 for counts out of range.  Launches on
+ * `stream` only: no allocation, no host synchronisation, no atomics, no block waits for another.  The kernels check what they
+ * dereference: foreign indices and foreign twin values give other numbers, never an access outside the arrays.
+ * TN_ERR_NULL: params or counts is NULL; TN_ERR_SHAPE: V < 0 or > 2^31 - 1, T < 0 or 3T > 2^31 - 1, capacity_segments < 0 or > 2^30,
+ * K outside [1, 256], a float / int32 pointer not 4-byte aligned, point_arc / curves / counts / workspace not 8-byte aligned;
+ * TN_ERR_UNSUPPORTED: a level that is not finite or not above its predecessor, in plane mode a normal that is not finite or all zero;
+ * TN_ERR_NULL: with V > 0 and T > 0 positions, temperature, triangles, twin or the workspace, and with capacity_segments > 0 an output
+ * array; TN_ERR_WORKSPACE: workspace_bytes too small (with V > 0 and T > 0).  All are returned before any launch.  V == 0 or T == 0:
+ * TN_OK, counts are zeroed, nothing is launched. */
+typedef struct tn_mesh_curve {
+    double length;
+    int32_t level, first_point, points, closed;
+    float mean_temperature, min_temperature, max_temperature;
+    int32_t first_face;
+} tn_mesh_curve;
+typedef struct tn_isoline_params {
+    double normal[3]; /* plane mode: the scalar is the signed distance along it (in units of its length) */
+    int32_t num_levels;
+    int32_t reserved;
+    double levels[256];
+} tn_isoline_params;
+size_t tn_mesh_isolines_workspace_bytes(int64_t num_vertices, int64_t num_triangles, int64_t capacity_segments);
+int tn_mesh_isolines(const float *positions, const float *temperature, const int32_t *triangles, int64_t num_vertices,
+                     int64_t num_triangles, const int32_t *twin, const float *scalar, const tn_isoline_params *params,
+                     float *point_positions, float *point_temperature, double *point_arc, int32_t *point_face,
+                     tn_mesh_curve *curves, int64_t capacity_segments, int64_t *counts, void *workspace, size_t workspace_bytes,
+                     void *stream);
+
 /* ------------------------------------------------------------------------------------------------------
  * Fused forward: Model.forward (collider) + ThermalNerfModel.get_outputs
  * [REF thermal_nerf_model.py:210-275]

@@ -124,6 +124,16 @@ class tn_register_params(C.Structure):
                 ("min_pairs", C.c_int32), ("reserved", C.c_int32 * 2)]
 
 
+class tn_mesh_curve(C.Structure):
+    _fields_ = [("length", C.c_double), ("level", C.c_int32), ("first_point", C.c_int32), ("points", C.c_int32), ("closed", C.c_int32),
+                ("mean_temperature", C.c_float), ("min_temperature", C.c_float), ("max_temperature", C.c_float),
+                ("first_face", C.c_int32)]
+
+
+class tn_isoline_params(C.Structure):
+    _fields_ = [("normal", C.c_double * 3), ("num_levels", C.c_int32), ("reserved", C.c_int32), ("levels", C.c_double * 256)]
+
+
 TN_REGISTER_POINT, TN_REGISTER_PLANE = 0, 1
 TN_REGISTER_STATUS = ("converged", "iterations", "too_few", "degenerate")  # the words of result[0]
 
@@ -301,6 +311,10 @@ SIGNATURES = {
                         + [_vp] * 8),
     "tn_mesh_register_workspace_bytes": (_sz, [_i64]),
     "tn_mesh_register": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _vp, _sz, _vp, _i64, C.POINTER(tn_register_params), _vp, _vp, _vp, _vp, _sz, _vp]),
+    "tn_mesh_half_edges_workspace_bytes": (_sz, [_i64, _i64]),
+    "tn_mesh_half_edges": (C.c_int, [_vp, _i64, _i64, _vp, _vp, _vp, _sz, _vp]),
+    "tn_mesh_isolines_workspace_bytes": (_sz, [_i64, _i64, _i64]),
+    "tn_mesh_isolines": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, C.POINTER(tn_isoline_params)] + [_vp] * 5 + [_i64, _vp, _vp, _sz, _vp]),
     "tn_mesh_tile": (_i32, []),
     "tn_mesh_scan_width": (_i32, []),
     "tn_mesh_workspace_bytes": (_sz, [_i32, _i32, _i32]),

@@ -13,16 +13,20 @@
 - project.py: the measured thermal photos projected onto a mesh: what the cameras measured at every vertex, from how many photos,
   how far they agree, where the model differs.
 - register.py: one survey's mesh into the frame of another's (iterated closest points, the start from a few picked pairs).
+- isolines.py: the half-edge twins of a mesh (closed, manifold, consistently oriented?) and its level-set curves: isotherms and plane
+  sections as ordered polylines with arc length and degrees along them.
 - ply.py: their PLY files.  _common.py: the argument checks they share.  cli.py: what the command lines under tools/ share.
 """
 from .closest import ClosestPoints, MeshDifference, mesh_closest, mesh_closest_into, mesh_difference  # noqa: F401
 from .components import (ComponentsInfo, MeshComponents, filter_components, mesh_components,  # noqa: F401
                          mesh_components_workspace_bytes, remove_small_components)
+from .isolines import (CURVE_DTYPE, MeshCurves, MeshHalfEdges, isotherms, mesh_half_edges, mesh_half_edges_workspace_bytes,  # noqa: F401
+                       mesh_isolines, mesh_isolines_into, mesh_isolines_workspace_bytes, mesh_sections)
 from .mesh import (MeshExporter, ThermalMesh, camera_pose, grid_dims, mesh_extract, mesh_params, mesh_scan_width,  # noqa: F401
                    mesh_tile, mesh_workspace_bytes, set_camera, tsdf_integrate, world_to_camera)
 from .neighbors import (Neighbors, estimate_normals, knn, knn_grid_resolution, knn_workspace_bytes, outlier_keep_mask,  # noqa: F401
                         pointcloud_normals, remove_statistical_outliers)
-from .ply import read_mesh_ply, read_ply, write_mesh_ply, write_ply  # noqa: F401
+from .ply import read_mesh_ply, read_ply, write_curves_ply, write_mesh_ply, write_ply  # noqa: F401
 from .pointcloud import (PointCloudExporter, ThermalPointCloud, pointcloud_append, pointcloud_params, scan_width,  # noqa: F401
                          subsample, subsample_indices, tile_rays, workspace_bytes, world_transform)
 from .project import (MeshMeasurement, ProjectedTemperatures, camera_records, mesh_measurement, project_images,  # noqa: F401

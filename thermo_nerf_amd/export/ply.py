@@ -211,3 +211,25 @@ def read_mesh_ply(path) -> Dict:
     if dtype is NORMAL_VERTEX_DTYPE:
         out["normals"] = _read_normals(vertex)
     return out
+
+
+def write_curves_ply(path, curves, temperature_bounds=None) -> Path:
+    """Write ``curves`` (a MeshCurves: level-set curves of a mesh, on the device or the host) to ``path`` as a line set: the P points
+    as vertices ``float x y z``, ``float temperature`` (16 bytes each), then one ``edge`` element per segment, ``int vertex1`` /
+    ``int vertex2`` (8 bytes each): consecutive points of a curve.  The comment lines are the mesh writer's, the bounds from
+    ``temperature_bounds``.  The same curves give the same bytes."""
+    pos, temp, table = _host(curves.positions), _host(curves.temperature), curves.curves
+    m = pos.shape[0]
+    if pos.shape != (m, 3) or temp.shape != (m,):
+        raise ValueError("positions [P,3] and temperature [P] must agree")
+    vertex = np.empty(m, dtype=np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("temperature", "<f4")]))
+    vertex["x"], vertex["y"], vertex["z"], vertex["temperature"] = pos[:, 0], pos[:, 1], pos[:, 2], temp
+    starts = [np.arange(int(row["first_point"]), int(row["first_point"]) + int(row["points"]) - 1, dtype=np.int32) for row in table]
+    first = np.concatenate(starts) if starts else np.zeros(0, np.int32)
+    if len(first) and (first.min() < 0 or first.max() + 1 >= m):
+        raise ValueError("a curve names a point outside [0, P)")
+    edge = np.empty(len(first), dtype=np.dtype([("vertex1", "<i4"), ("vertex2", "<i4")]))
+    edge["vertex1"], edge["vertex2"] = first, first + 1
+    lines = header(m, temperature_bounds).split("\n")[:5]  # up to ``element vertex``
+    lines += [*_PROPERTIES[:3], _PROPERTIES[-1], f"element edge {len(edge)}", "property int vertex1", "property int vertex2", "end_header"]
+    return _write(path, "\n".join(lines) + "\n", vertex, edge)
