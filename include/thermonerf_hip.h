@@ -1265,6 +1265,88 @@ int tn_mesh_isolines(const float *positions, const float *temperature, const int
                      tn_mesh_curve *curves, int64_t capacity_segments, int64_t *counts, void *workspace, size_t workspace_bytes,
                      void *stream);
 
+/* Planar patches of an indexed triangle list: the faces joined across edges while the angle between their normals stays under a
+ * limit (walls, floors, roof planes), and per patch its fitted plane, area, flatness, deviation from the plane and area-weighted mean /
+ * min / max temperature.  With min_cos = -1 the patches are the EDGE-connected components (tn_mesh_components is vertex connectivity).
+ * positions [V, 3] floats, temperature [V] floats, triangles [T, 3] int32, twin [3T] int32 as tn_mesh_half_edges writes it (foreign
+ * data: a value is used as an index only inside [0, 3T)), V = num_vertices, T = num_triangles.  min_cos is the cosine of the largest
+ * angle between the normals of two joined faces, taken on the host: the device never calls libm.  Every output is defined to the bit.
+ * add / sub / mul / div / sqrt below are single correctly rounded fp64 operations, nothing is contracted; (double) of a float is
+ * exact, (float) of a double rounds to nearest even.
+ *   face f, indices i0 i1 i2, positions p0 p1 p2, temperatures t0 t1 t2:
+ *     c, n2, area, centroid m, tf   the expressions of tn_mesh_regions: e1 = sub(p1, p0), e2 = sub(p2, p0) per component; c = (sub(
+ *               mul(e1y, e2z), mul(e1z, e2y)), sub(mul(e1z, e2x), mul(e1x, e2z)), sub(mul(e1x, e2y), mul(e1y, e2x))); n2 = add(add(
+ *               mul(cx, cx), mul(cy, cy)), mul(cz, cz)); area = mul(0.5, sqrt(n2)); m per axis div(add(add(p0, p1), p2), 3.0);
+ *               tf = (float)div(add(add((double)t0, (double)t1), (double)t2), 3.0).
+ *     GEOMETRIC the three indices in [0, V) and distinct, all nine coordinates finite, n2 > 0.
+ *     THERMAL   geometric and all three temperatures finite.  A face with a NaN temperature is still part of its wall.
+ *     u         the unit normal: len = sqrt(n2), u = (div(cx, len), div(cy, len), div(cz, len)).
+ *   JOINED      faces f != g are joined iff both are geometric, some half-edge h of one has twin[h] in [0, 3T) with twin[h] / 3 the
+ *               other, and add(add(mul(ufx, ugx), mul(ufy, ugy)), mul(ufz, ugz)) >= min_cos (symmetric in f and g).
+ *   patches     a patch is a class of the transitive closure of JOINED over the geometric faces; a lone geometric face is a patch.  Its
+ *               LABEL is the smallest face index in it; patches are numbered q = 0 .. Q-1 in ascending label; a patch's faces are
+ *               taken in ascending face index.  The criterion is adjacency chaining: a gently curved surface whose neighbouring faces
+ *               all stay under the angle is ONE patch; flatness and rms_deviation show it.
+ *   face_patch  (int32 [T], always fully written): q of a geometric face, -1 of every other.
+ *   SUM2(list)  the ordered sum of tn_mesh_regions: consecutive blocks of 256 entries from the list's start (the last may be short),
+ *               each accumulated from +0.0 in list order, s = add(s, x); the block sums then accumulated from +0.0 in block order.
+ *   tn_mesh_patch, row q of `patches` (136 bytes), over the patch's faces f:
+ *     area              SUM2(area_f)
+ *     thermal_area      SUM2(area_f of a thermal face, +0.0 of every other)
+ *     N (not stored)    the vector area, per axis a: SUM2(mul(0.5, c_f,a))
+ *     centroid[a]       div(SUM2(mul(area_f, m_f,a)), area)
+ *     plane             nn = add(add(mul(Nx, Nx), mul(Ny, Ny)), mul(Nz, Nz)).  With nn > 0: plane[a] = div(N_a, sqrt(nn)) for a = 0, 1, 2,
+ *                       plane[3] = add(add(mul(plane[0], centroid[0]), mul(plane[1], centroid[1])), mul(plane[2], centroid[2])): the
+ *                       points x of the plane have dot(plane[0..2], x) = plane[3].  With nn == 0: four +0.0.
+ *     flatness          (float)div(sqrt(nn), area): 1 for a flat patch, 0 for a closed surface; +0.0 with nn == 0
+ *     rms_deviation     per face and corner i: e_i = add(add(mul(nx, sub(p_ix, cx)), mul(ny, sub(p_iy, cy))), mul(nz, sub(p_iz, cz)))
+ *                       with n = plane[0..2], c = centroid and the position widened to double; s = add(add(e0, e1), e2);
+ *                       term_f = mul(div(area_f, 12.0), add(add(add(mul(e0, e0), mul(e1, e1)), mul(e2, e2)), mul(s, s))) — the
+ *                       integral of the squared distance over the triangle, not just its centroid;
+ *                       rms_deviation = (float)sqrt(div(SUM2(term_f), area))
+ *     max_deviation     (float) of the largest |e_i| over the patch's faces and corners (a maximum is order-free).  With nn == 0 both
+ *                       deviations are the NaN 0x7fc00000.
+ *     mean_temperature  (float)div(SUM2(mul(area_f, (double)tf_f) of a thermal face, +0.0 of every other), thermal_area)
+ *     min_temperature, max_temperature   of tf_f over the thermal faces;  bounds: min x y z, max x y z over the positions of the
+ *                       patch's vertices.  Both in the numbers' order with -0.0 below +0.0.  With thermal_area == 0 the mean and both
+ *                       extremes are the NaN 0x7fc00000.
+ *     label, faces, thermal_faces   as above; the numbers of its faces and of its thermal faces;  reserved = 0
+ *   totals (double [2], OVERWRITTEN): [0] SUM2 of area_f over the geometric faces in ascending face index (the mesh's area), [1] the
+ *               same over the thermal faces.
+ *   counts (device int64 [3], OVERWRITTEN): [0] Q — the FULL number; rows at or beyond capacity_patches are not written (0 with
+ *               patches NULL: the sizing call) —, [1] the geometric faces, [2] the half-edges h whose face is joined with the face of
+ *               twin[h] (twice the joining edges of a symmetric table).
+ * How: one thread per face writes a 112-byte record (the nine products, tf, the face's box) and its unit normal; the geometric and the
+ * thermal faces are compacted in order (count, one-block scan, emit); one thread per half-edge hooks joined faces in a lock-free
+ * union-find over the T faces (relaxed agent-scope loads, compare-and-swap of the higher root under the lower), a flatten gives every
+ * face its label; tn_sort_pairs of (label, face) puts a patch's faces side by side in face order and the patches in label order, so
+ * count / scan / emit over the heads of the runs numbers the patches and finds their faces without an atomic; one thread per
+ * 256-block walks its records into a partial, one thread per patch walks its partials (its faces when they are at most 256) and
+ * writes centroid and plane; one thread per face measures its corners against its row's plane, and the same two levels finish the
+ * row.  The totals take the two steps over the two compacted lists.  workspace: tn_mesh_patches_workspace_bytes(V, T) device bytes,
+ * 8-byte aligned; 0 for counts out of range.  Launches on `stream` only: no allocation, no host synchronisation, no float atomics
+ * (the integer ones are the union-find's, the count of [2] — one per block — and the sort's), no block waits for another.  The
+ * kernels check what they dereference: a foreign index or twin value gives other numbers, never an access outside the arrays.
+ * TN_ERR_NULL: counts or totals is NULL; positions, temperature, twin or the workspace with V > 0 and T > 0; triangles or face_patch
+ * with T > 0; patches with capacity_patches > 0; TN_ERR_SHAPE: V < 0 or > 2^31 - 1, T < 0 or 3T > 2^31 - 1, a negative capacity, a
+ * float / int32 pointer not 4-byte aligned, patches / totals / counts / workspace not 8-byte aligned; TN_ERR_UNSUPPORTED: min_cos a
+ * NaN or outside [-1, 1]; TN_ERR_WORKSPACE: workspace_bytes too small (with V > 0 and T > 0).  All are returned before any launch,
+ * and in the order of the code: counts / totals, the shape, min_cos, the other pointers, the alignment, the workspace.  V == 0 or
+ * T == 0: TN_OK, counts and totals are zeroed and face_patch filled with -1 by memsets, nothing is launched. */
+typedef struct tn_mesh_patch {
+    double area, thermal_area;
+    double plane[4];
+    double centroid[3];
+    float flatness, rms_deviation, max_deviation;
+    float mean_temperature, min_temperature, max_temperature;
+    float bounds[6];
+    int32_t label, faces, thermal_faces, reserved;
+} tn_mesh_patch;
+size_t tn_mesh_patches_workspace_bytes(int64_t num_vertices, int64_t num_triangles);
+int tn_mesh_patches(const float *positions, const float *temperature, const int32_t *triangles, int64_t num_vertices,
+                    int64_t num_triangles, const int32_t *twin, double min_cos, tn_mesh_patch *patches, int64_t capacity_patches,
+                    int32_t *face_patch, int64_t *counts, double *totals, void *workspace, size_t workspace_bytes, void *stream);
+
 /* ------------------------------------------------------------------------------------------------------
  * Fused forward: Model.forward (collider) + ThermalNerfModel.get_outputs
  * [REF thermal_nerf_model.py:210-275]

@@ -134,6 +134,13 @@ class tn_isoline_params(C.Structure):
     _fields_ = [("normal", C.c_double * 3), ("num_levels", C.c_int32), ("reserved", C.c_int32), ("levels", C.c_double * 256)]
 
 
+class tn_mesh_patch(C.Structure):
+    _fields_ = [("area", C.c_double), ("thermal_area", C.c_double), ("plane", C.c_double * 4), ("centroid", C.c_double * 3),
+                ("flatness", C.c_float), ("rms_deviation", C.c_float), ("max_deviation", C.c_float), ("mean_temperature", C.c_float),
+                ("min_temperature", C.c_float), ("max_temperature", C.c_float), ("bounds", C.c_float * 6), ("label", C.c_int32),
+                ("faces", C.c_int32), ("thermal_faces", C.c_int32), ("reserved", C.c_int32)]
+
+
 TN_REGISTER_POINT, TN_REGISTER_PLANE = 0, 1
 TN_REGISTER_STATUS = ("converged", "iterations", "too_few", "degenerate")  # the words of result[0]
 
@@ -315,6 +322,8 @@ SIGNATURES = {
     "tn_mesh_half_edges": (C.c_int, [_vp, _i64, _i64, _vp, _vp, _vp, _sz, _vp]),
     "tn_mesh_isolines_workspace_bytes": (_sz, [_i64, _i64, _i64]),
     "tn_mesh_isolines": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, C.POINTER(tn_isoline_params)] + [_vp] * 5 + [_i64, _vp, _vp, _sz, _vp]),
+    "tn_mesh_patches_workspace_bytes": (_sz, [_i64, _i64]),
+    "tn_mesh_patches": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _vp, C.c_double, _vp, _i64, _vp, _vp, _vp, _vp, _sz, _vp]),
     "tn_mesh_tile": (_i32, []),
     "tn_mesh_scan_width": (_i32, []),
     "tn_mesh_workspace_bytes": (_sz, [_i32, _i32, _i32]),

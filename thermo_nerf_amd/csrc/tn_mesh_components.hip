@@ -19,65 +19,18 @@
 // spinning on another thread's progress, no grid barrier, no cooperative launch).  Nothing in any output depends on the order in
 // which threads arrive: the union-find's TREE does, its roots do not, and sums and maxima of integers are exact in any order.
 //
-// THE UNION-FIND.  Invariant I: parent[x] <= x, and parent[x] is only ever replaced by an ANCESTOR of x (a node reachable from x by
-// following parent).  x is a root iff parent[x] == x.  Two kinds of writes exist:
-//   * hook: atomicCAS(&parent[hi], hi, lo) with lo < hi.  It can only succeed while hi is a root, and then makes it a non-root
-//     below lo.  So only roots are ever CAS-written, and a node that has stopped being a root never becomes one again: every later
-//     CAS on it compares against hi and fails, and halving (below) never writes x into parent[x].
-//   * halving, inside find: parent[x] <- parent[parent[x]], an atomic store to a node that was SEEN as a non-root (hence is one
-//     for good), of a value that was an ancestor of x when it was read.  Ancestors stay ancestors: every write replaces a parent by
-//     one of ITS ancestors, which keeps the old parent's chain below the new one.  Two racing halvings may leave the farther or the
-//     nearer ancestor; both keep I.  Without halving a triangle strip hooks into a chain of depth O(V) and the walks are quadratic.
-// Since parent[x] < x for a non-root, the forest has no cycle and every walk ends.  unite(a, b): find both roots; while they differ,
-// CAS the higher under the lower; a failed CAS returns the value it found, which is strictly smaller than hi (hi was no longer a
-// root: parent[hi] < hi), and the loop continues from find of that value and lo, both below hi — the larger of the pair strictly
-// decreases, so the loop ends after at most V rounds whatever the other threads do; nobody waits for anybody.
-// A STALE READ IS HARMLESS: every value parent[x] ever held is an ancestor of x for good, so a walk through old values is only
-// longer, and it ends at a node r that was a root of x's tree when read.  If r has since been hooked, either the two walks still
-// met in the same r (then a and b are connected: both have r as an ancestor) or the CAS, which acts on the true value, fails
-// and hands back the fresh one.  A CAS that succeeds with a stale `lo` that is no longer a root links hi below a non-root: lo's
-// tree then contains hi's, which is all that is asked.  parent is read in the hook kernel with relaxed agent-scope atomic loads
-// (served by the memory side, not by a CU's cache that no other CU's store ever refreshes), so "stale" is a matter of microseconds.
-// After the hook kernel every valid triangle's vertices share a root; roots only merge, so they still do at its end, and no two
-// components were ever joined without a triangle.  The root is the smallest index of its tree (I).  The kernel boundary is the only
-// ordering the flatten kernel needs; it reads parent with plain loads while other threads already store roots into it, which by
-// the same argument (a root is an ancestor) changes no result.
+// THE UNION-FIND (load_parent / find_root / unite, with the proof that every walk ends, that a stale read is harmless and that the
+// root is the smallest index of its tree) is tn_union_find.h, shared with tn_mesh_patches.hip.  After the hook kernel every valid
+// triangle's vertices share a root, and no two components were ever joined without a triangle.
 #include "tn_device.h"
 #include "tn_scan.h"
+#include "tn_union_find.h"
 
 using namespace tn;
 
 namespace {
 
 constexpr int kTile = 256;  // vertices / triangles per tile = threads per block of every kernel but the scan (tn_mesh_tile())
-
-__device__ __forceinline__ int load_parent(const int *parent, int x) {
-    return __hip_atomic_load(parent + x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// the root of x as this thread sees it, halving the path on the way
-__device__ __forceinline__ int find_root(int *parent, int x) {
-    int p = load_parent(parent, x);
-    while (p != x) {
-        const int g = load_parent(parent, p);
-        if (g != p) __hip_atomic_store(parent + x, g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // x is a non-root, g an ancestor
-        x = p;
-        p = g;
-    }
-    return x;
-}
-
-__device__ __forceinline__ void unite(int *parent, int a, int b) {
-    a = find_root(parent, a);
-    b = find_root(parent, b);
-    while (a != b) {
-        const int hi = a > b ? a : b, lo = a > b ? b : a;
-        const int found = atomicCAS(parent + hi, hi, lo);
-        if (found == hi) return;
-        a = find_root(parent, found);  // found < hi
-        b = lo;                        // (a root when read; a stale one is still in its tree)
-    }
-}
 
 __device__ __forceinline__ bool valid_triangle(const int *__restrict__ tri, long long t, int num_vertices, int (&v)[3]) {
     v[0] = tri[3 * t], v[1] = tri[3 * t + 1], v[2] = tri[3 * t + 2];

@@ -15,6 +15,8 @@
 - register.py: one survey's mesh into the frame of another's (iterated closest points, the start from a few picked pairs).
 - isolines.py: the half-edge twins of a mesh (closed, manifold, consistently oriented?) and its level-set curves: isotherms and plane
   sections as ordered polylines with arc length and degrees along them.
+- patches.py: the planar patches of a mesh (walls, floors, roof planes) joined across edges under an angle limit, with their plane,
+  area, flatness and degrees; the edge-connected components; the view that looks straight at a patch.
 - ply.py: their PLY files.  _common.py: the argument checks they share.  cli.py: what the command lines under tools/ share.
 """
 from .closest import ClosestPoints, MeshDifference, mesh_closest, mesh_closest_into, mesh_difference  # noqa: F401
@@ -26,6 +28,8 @@ from .mesh import (MeshExporter, ThermalMesh, camera_pose, grid_dims, mesh_extra
                    mesh_tile, mesh_workspace_bytes, set_camera, tsdf_integrate, world_to_camera)
 from .neighbors import (Neighbors, estimate_normals, knn, knn_grid_resolution, knn_workspace_bytes, outlier_keep_mask,  # noqa: F401
                         pointcloud_normals, remove_statistical_outliers)
+from .patches import (PATCH_BYTES, PATCH_DTYPE, MeshPatches, edge_components, mesh_patches_into,  # noqa: F401
+                      mesh_patches_workspace_bytes, patch_view, planar_patches)
 from .ply import read_mesh_ply, read_ply, write_curves_ply, write_mesh_ply, write_ply  # noqa: F401
 from .pointcloud import (PointCloudExporter, ThermalPointCloud, pointcloud_append, pointcloud_params, scan_width,  # noqa: F401
                          subsample, subsample_indices, tile_rays, workspace_bytes, world_transform)
