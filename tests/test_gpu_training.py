@@ -10,7 +10,9 @@ entry by entry, with inputs whose sums are exact in fp32 (tests/table_gradient_r
 — a whole-table L2 norm is dominated by the crowded coarse entries and would not see a lost record at a fine level.  The per-ray
 kernels above them (tn_ray_render_bwd, tn_weights_bwd, tn_composite_bwd, the distortion and interlevel losses, tn_image_losses) are
 held element by element to tests/ray_losses_reference.py by tests/test_gpu_ray_losses.py: exact on dyadic and single-interval
-inputs, bounded by counted roundings elsewhere."""
+inputs, bounded by counted roundings elsewhere.  The forward half of that chain (tn_sample_pdf, tn_weights_fwd, tn_composite_fwd,
+tn_depth_fwd, tn_sample_initial, the frustum kernels, tn_ray_render_fwd / tn_ray_render_depth_fwd against the modular calls) is held
+the same way to tests/ray_forward_reference.py by tests/test_gpu_ray_forward.py."""
 import copy
 import ctypes as C
 
