@@ -673,10 +673,11 @@ int tn_mesh_simplify(const float *positions, const uint8_t *colors, const float 
  *               regions NULL: the sizing call) —, [1] the selected faces, [2] the usable faces.
  * How: one thread per face writes a 96-byte record (the five products, tf, the face's box, its hottest and coldest corner) and a
  * copy of the index list in which a face outside the window is invalid; the usable and the selected faces are compacted in order
- * (count, one-block scan, emit); tn_mesh_components labels the copy; the roots that own a face are numbered and their face and block
- * counts summed by a second count / scan / emit over the vertices; tn_sort_pairs of (label, face) puts a region's faces side by
- * side in face order; one thread per 256-block walks its records into a partial, one thread per region walks its partials; the two
- * totals take the same two steps over the two compacted lists.  workspace: tn_mesh_regions_workspace_bytes(V, T) device bytes,
+ * (count, one-block scan, emit); tn_mesh_components labels the copy; tn_sort_pairs of (label, face) puts a region's faces side by side in
+ * face order, the regions in ascending label; the first position of every run is numbered by a count / scan / emit over the sorted
+ * positions (a region's faces are the distance to the next run), the 256-blocks by one over the regions; one thread per 256-block
+ * walks its records into a partial, one thread per region walks its partials; the two totals take the same two steps over the two
+ * compacted lists.  workspace: tn_mesh_regions_workspace_bytes(V, T) device bytes,
  * 8-byte aligned; 0 for counts out of range.  Launches on `stream` only: no allocation, no host synchronisation, no float atomics
  * (the integer ones are tn_mesh_components' and the sort's), no block waits for another.  The kernels check what they dereference:
  * a foreign index gives other numbers, never an access outside the arrays.

@@ -220,6 +220,13 @@ def test_patches_of_1_255_256_and_257_faces():
     tri = tri[np.random.default_rng(3).permutation(len(tri))]
     want, _ = check(_with_temperature(pos, tri, 3), COS10)
     assert sorted(want["patches"]["faces"].tolist()) == [1, 255, 256, 257, 513]
+    # every temperature -0.0: a sum is +0.0 whether the patch is walked by its row's thread (up to 256 faces) or has partials (257,
+    # 513), while the extremes keep the sign
+    want, got = check((np.asarray(pos, F), np.full(len(pos), -0.0, F), np.asarray(tri, np.int32)), COS10)
+    rows = got["patches"][:5]
+    assert sorted(rows["faces"].tolist()) == [1, 255, 256, 257, 513] and (rows["thermal_area"] > 0.0).all()
+    assert R.bits(rows["mean_temperature"]).tolist() == [0x00000000] * 5
+    assert R.bits(rows["min_temperature"]).tolist() == R.bits(rows["max_temperature"]).tolist() == [0x80000000] * 5
 
 
 @functools.lru_cache(maxsize=None)

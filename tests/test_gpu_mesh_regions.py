@@ -114,16 +114,24 @@ def test_literal_cases_through_the_kernel(name):
 
 # ---- one region of n faces ------------------------------------------------------------------------------------------------------------
 
-@pytest.mark.parametrize("faces", [1, 255, 256, 257, 513, 65537])
+@pytest.mark.parametrize("faces", [1, 255, 256, 257, 513, 65537, 262401])
 def test_one_region_of_exactly_n_faces(faces):
     pos, tri = R.strip(faces, R.STRIP_SEED)
     temp = np.random.default_rng(faces).uniform(18.0, 31.0, len(pos)).astype(F)
     want, got = check((pos, temp, tri), OPEN)
     assert want["counts"].tolist() == [1, faces, faces] and int(want["regions"]["faces"][0]) == faces
     assert want["regions"]["area"][0] == want["totals"][0] == want["totals"][1]
-    if faces == 65537:
+    if faces >= 65537:
         assert faces > 256 * 256, "more than 256 partials: the second level is itself longer than a block"
-        check((pos, temp, tri), (24.0, 25.0))  # the same strip cut into many short regions
+        many, _ = check((pos, temp, tri), (24.0, 25.0))  # the same strip cut into many short regions
+        if faces == 262401:  # 1026 tiles of sorted positions: the regions are numbered over more than one pass of the scan block
+            assert -(-faces // 256) > 1024 and many["counts"][0] > 10000
+    if faces in (1, 257):
+        # every temperature -0.0: a sum is +0.0 through one partial (1 face) and through two (257), while the extremes keep the sign
+        want, got = check((pos, np.full(len(pos), -0.0, F), tri), OPEN)
+        row = rows_of(got, 1)[0]
+        three = np.array([row[n] for n in ("mean_temperature", "min_temperature", "max_temperature")], F)
+        assert row["area"] > 0.0 and R.bits(three).tolist() == [0x00000000, 0x80000000, 0x80000000]
 
 
 # ---- the lattice ------------------------------------------------------------------------------------------------------------------------

@@ -162,8 +162,67 @@ def test_header_makefile_ctypes_table_and_library_agree_on_the_new_entries():
         code = open(os.path.join(ROOT, "thermo_nerf_amd", "csrc", source)).read()
         assert '#include "tn_union_find.h"' in code and "unite(" in code and "int find_root(" not in code, source
     assert "int find_root(" in shared and "void unite(" in shared and "int load_parent(" in shared
+    # the grouped sums, the two lists and the face loader of regions and patches are tn_group_sum.h's, and the small host helpers
+    # tn_device.h's: no source carries a copy
+    assert " tn_group_sum.h " in makefile
+    for source in ("tn_mesh_regions.hip", "tn_mesh_patches.hip"):
+        code = open(os.path.join(ROOT, "thermo_nerf_amd", "csrc", source)).read()
+        assert '#include "tn_group_sum.h"' in code and "group_sum(" in code, source
+        assert "total_blocks_kernel(" not in code and "block_sums_kernel(" not in code, source
+    shared = open(os.path.join(ROOT, "thermo_nerf_amd", "csrc", "tn_group_sum.h")).read()
+    assert "total_blocks_kernel(" in shared and "block_sums_kernel(" in shared and "Face load_face(" in shared
+    csrc = os.path.join(ROOT, "thermo_nerf_amd", "csrc")
+    holders = sorted(n for n in os.listdir(csrc) if n.endswith((".hip", ".h")) and "ints_bytes(long long" in open(os.path.join(csrc, n)).read())
+    assert holders == ["tn_device.h"]
     # the size function runs without a device; the error codes that come before any launch too
     load = _hip.load()
     assert lib.tn_mesh_patches_workspace_bytes(-1, 0) == 0 and load.tn_mesh_patches_workspace_bytes(8, 2 ** 30) == 0
     assert load.tn_mesh_patches_workspace_bytes(8, 12) > 0
     assert load.tn_mesh_patches(None, None, None, 8, 12, None, 0.5, None, 0, None, None, None, None, 0, None) == -1
+
+
+def test_workspace_sizes_against_those_of_the_separate_implementations():
+    """(V, T) -> the bytes the two entries asked for while each carried its own grouped sum: patches asks for exactly as much, regions
+    (which lost its three arrays of vertex-tile counts and keeps its T / 256 + min(V / 3, T) partials) for no more"""
+    before = {(8, 12): (5080, 4408), (300, 257): (60312, 56304), (110162, 220320): (49841528, 39268464),
+              (1048576, 2097152): (474415136, 373773688)}
+    load = _hip.load()
+    for (v, t), (patches, regions) in before.items():
+        assert load.tn_mesh_patches_workspace_bytes(v, t) == patches, (v, t)
+        assert 0 < load.tn_mesh_regions_workspace_bytes(v, t) <= regions, (v, t)
+    # many more faces than vertices: the bound on the partials falls back on the regions the vertices allow
+    assert 0 < load.tn_mesh_regions_workspace_bytes(8, 2 ** 20) <= 160973200
+
+
+def test_the_bench_tool_finds_every_kernel_of_the_call_under_the_name_a_trace_gives_it():
+    """tools/mesh_patches_bench.py matches traced kernel names whole: the kernels of tn_mesh_patches.hip and of tn_group_sum.h, as a
+    trace demangles them, are the tool's groups without the sort's three"""
+    import importlib.util
+    import sys
+
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    try:
+        spec = importlib.util.spec_from_file_location("mesh_patches_bench_tool", os.path.join(ROOT, "tools", "mesh_patches_bench.py"))
+        tool = importlib.util.module_from_spec(spec)
+        spec.loader.exec_module(tool)
+    finally:
+        sys.path.remove(os.path.join(ROOT, "tools"))
+    traced = ["(anonymous namespace)::scan_faces_kernel(tn::FaceLists, long long)",
+              "(anonymous namespace)::total_blocks_kernel(tn::FaceLists, long long, char const*, long long, long long, double*)",
+              "(anonymous namespace)::count_heads_kernel(tn::Groups, long long*)",
+              "(anonymous namespace)::rows_kernel(tn::Groups, (anonymous namespace)::Acc const*, (anonymous namespace)::Acc const*, long long, tn_mesh_patch*)",
+              "void (anonymous namespace)::block_sums_kernel<(anonymous namespace)::Acc>(tn::Groups, long long, (anonymous namespace)::Acc const*, (anonymous namespace)::Acc*)",
+              "void (anonymous namespace)::block_sums_kernel<(anonymous namespace)::Dev>(tn::Groups, long long, (anonymous namespace)::Dev const*, (anonymous namespace)::Dev*)"]
+    assert [tool.short_name(n) for n in traced] == ["scan_faces_kernel", "total_blocks_kernel", "count_heads_kernel", "rows_kernel",
+                                                    "block_sums_kernel<Acc>", "block_sums_kernel<Dev>"]
+    assert all(tool.short_name(n) in tool.GROUP_OF for n in traced)
+    # every kernel the two files define, under the name the tool lists; a kernel in a named namespace or a template over the record
+    # where the tool lists a plain name would drop out of the shares without an error
+    csrc = os.path.join(ROOT, "thermo_nerf_amd", "csrc")
+    shared, own = open(os.path.join(csrc, "tn_group_sum.h")).read(), open(os.path.join(csrc, "tn_mesh_patches.hip")).read()
+    kernels = re.compile(r"(template <typename R>\n)?__global__ void (?:__launch_bounds__\(\w+\)\s+)?(\w+)\(")
+    assert "static __global__" not in shared and shared.index("\nnamespace {\n") < shared.index("__global__ void") < shared.index("\n}  // namespace\n")
+    named = set()
+    for template, name in kernels.findall(shared) + kernels.findall(own):
+        named |= {name + "<Acc>", name + "<Dev>"} if template else {name}
+    assert named == set(tool.GROUP_OF) - {"histogram_kernel", "scatter_kernel", "scan_kernel"}, named ^ set(tool.GROUP_OF)

@@ -693,6 +693,14 @@ namespace tn {  // host side: the entry points' argument checks and grid sizes (
 inline bool misaligned(const void *p, uintptr_t a) { return reinterpret_cast<uintptr_t>(p) % a != 0; }
 inline long long ceil_div(long long n, long long d) { return (n + d - 1) / d; }
 inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
+// the bytes of n ints inside a workspace whose next array is 8-byte aligned
+inline size_t ints_bytes(long long n) { return ((size_t)n * sizeof(int) + 7) / 8 * 8; }
+// the bits of the largest key of a tn_sort_pairs call, at least one
+inline int key_bits(unsigned long long max_key) {
+    int bits = 1;
+    while (bits < 64 && (max_key >> bits) != 0) ++bits;
+    return bits;
+}
 // the vertex and face counts every mesh entry refuses: 3 T must fit an int
 inline bool bad_counts(int64_t v, int64_t t) { return v < 0 || v > 0x7fffffffLL || t < 0 || 3 * t > 0x7fffffffLL; }
 constexpr long long kCUs = 256;  // compute units of the chip: a grid-stride kernel's cap is kCUs x its resident blocks per CU

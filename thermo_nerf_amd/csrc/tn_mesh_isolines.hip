@@ -36,8 +36,6 @@ constexpr int kMaxLevels = 256;  // levels of one call
 constexpr long long kMaxCapacity = 1LL << 30;  // segments of one call: 2 * capacity points are int32 rows, ranks stay below 2^31
 
 inline long long tiles_of(long long n) { return ceil_div(n, kTile); }
-inline size_t ints_bytes(long long n) { return ((size_t)n * sizeof(int) + 7) / 8 * 8; }
-
 __device__ __forceinline__ bool finite64(double x) { return fabs(x) <= 1.7976931348623157e308; }  // (a NaN fails)
 
 // ---- half-edges ------------------------------------------------------------------------------------------------------------------------
@@ -104,13 +102,6 @@ edge_classes_kernel(const unsigned long long *__restrict__ sorted, const int *__
     __syncthreads();
     block_rank<kTile>(members == 2 && same, total[3]);
     if (threadIdx.x < 4 && total[threadIdx.x] > 0) atomicAdd(&counts[threadIdx.x], (unsigned long long)total[threadIdx.x]);
-}
-
-inline int key_bits(long long num_vertices) {  // the keys are 0 .. V * V
-    const unsigned long long top = (unsigned long long)num_vertices * (unsigned long long)num_vertices;
-    int bits = 1;
-    while (bits < 64 && (top >> bits) != 0) ++bits;
-    return bits;
 }
 
 // the workspace of tn_mesh_half_edges, in order: the keys, the sorted keys, the sorted half-edges, the sort's own workspace
@@ -623,7 +614,8 @@ int tn_mesh_half_edges(const int32_t *triangles, int64_t num_triangles, int64_t 
     const unsigned blocks = (unsigned)tiles_of(3 * nt);
     hipLaunchKernelGGL(edge_keys_kernel, dim3(blocks), dim3(kTile), 0, s, triangles, nt, nv, l.keys, twin);
     TN_LAUNCH_CHECK();
-    const int code = tn_sort_pairs(reinterpret_cast<const uint64_t *>(l.keys), nullptr, 3 * num_triangles, key_bits(nv),
+    const int code = tn_sort_pairs(reinterpret_cast<const uint64_t *>(l.keys), nullptr, 3 * num_triangles,
+                                   key_bits((unsigned long long)nv * (unsigned long long)nv),  // the keys are 0 .. V * V
                                    reinterpret_cast<uint64_t *>(l.sorted), l.order, l.sort, l.sort_bytes, stream);
     if (code != TN_OK) return code;
     hipLaunchKernelGGL(edge_classes_kernel, dim3(blocks), dim3(kTile), 0, s, l.sorted, l.order, triangles, nt, nv, twin,

@@ -362,8 +362,6 @@ inline bool host_finite(double x) { return x - x == 0.0; }
 
 inline long long tiles_of(long long n) { return ceil_div(n, kTile); }
 
-inline size_t ints_bytes(long long n) { return ((size_t)n * sizeof(int) + 7) / 8 * 8; }
-
 // the workspace, in order: the key plane, the face records, the partials, three arrays of tile counts, the number of large faces,
 // the flags and the list of the large faces
 struct Layout {

@@ -207,8 +207,6 @@ inline long long tiles_of(long long n) { return ceil_div(n, kTile); }
 
 inline size_t keys_bytes(long long n) { return (size_t)n * sizeof(unsigned long long); }
 
-inline size_t ints_bytes(long long n) { return ((size_t)n * sizeof(int) + 7) / 8 * 8; }
-
 inline bool two_sorts(long long num_vertices) { return 3 * bit_length((unsigned long long)num_vertices) + 1 > 64; }
 
 // the workspace, in order: per vertex the keys, the sorted keys, five int arrays (order, heads, rank, used, cluster_out) and the tile

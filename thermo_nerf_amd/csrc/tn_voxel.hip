@@ -69,8 +69,6 @@ inline long long tiles_of(long long n) { return ceil_div(n, kTile); }
 
 inline size_t keys_bytes(long long n) { return (size_t)n * sizeof(unsigned long long); }
 
-inline size_t ints_bytes(long long n) { return ((size_t)n * sizeof(int) + 7) / 8 * 8; }
-
 }  // namespace
 
 extern "C" {
