@@ -517,6 +517,80 @@ int tn_mesh_smooth(const float *positions_in, const int32_t *triangles, int64_t 
                    const int32_t *offsets, const int32_t *corners, int32_t iterations, float lambda, float mu, float *positions_out,
                    float *scratch, void *stream);
 
+/* The NaN-aware smoothing of a per-vertex scalar and its surface gradient (degrees Celsius per world unit: where the temperature
+ * changes fastest), on tn_mesh_incidence's lists: offsets / corners are tn_mesh_incidence's of the SAME triangles and V.  positions
+ * [V, 3] floats, values [V] floats, triangles [T, 3] int32, V = num_vertices, T = num_triangles.  Every output is defined to the bit.
+ * add / sub / mul / div / sqrt below are single correctly rounded fp64 operations, nothing is contracted; (double) of a float is
+ * exact, (float) of a double rounds to nearest even.  FINITE: neither a NaN nor an infinity.
+ * tn_mesh_scalar_smooth: values_out (float [V]) = values_in after `iterations` >= 0 iterations; scratch: float [V].
+ *   A PASS with factor k, src -> dst (Jacobi: src is only read, dst only written, one thread per vertex): s = +0.0, n = 0; for the
+ *   corners of v's list in list order, corner (t, j) — skipped, as in tn_mesh_smooth, when it lies outside [0, 3T) or its triangle
+ *   is not VALID (all three indices in [0, V)) —: q = src[t[(j + 1) % 3]], r = src[t[(j + 2) % 3]]; for each of the two that is
+ *   finite, q first: s = add(s, (double)x), n += 1.  With p = src[v]:
+ *     n == 0                       dst[v] = p, the same bits
+ *     otherwise m = div(s, (double)n), and
+ *       p finite                   dst[v] = (float)add((double)p, mul((double)k, sub(m, (double)p)))
+ *       p not finite, fill != 0    dst[v] = (float)m
+ *       p not finite, fill == 0    dst[v] = p, the same bits
+ *   A value that is not finite is never a partner: a NaN spreads nowhere, and with `fill` a hole closes by one ring of vertices
+ *   per pass — each pass reads only src, so the order in which it closes depends on no schedule.  A vertex in no valid triangle
+ *   and an island all of whose vertices lack a value stay as they are.
+ *   An ITERATION is a pass with lambda, then a pass with mu; with mu == 0 it is the pass with lambda alone (plain diffusion, the
+ *   low-pass a noisy scalar wants; the pair with lambda > 0, mu < -lambda is Taubin's filter, which keeps amplitudes).  Any finite
+ *   pair is accepted.  lambda == 0 and mu == 0 with `fill` fills the holes and moves no other value: add(p, mul(0, d)) is the
+ *   number p for finite p and d (p == -0.0 becomes +0.0 where the product is +0.0; every other p keeps its bits).
+ *   The passes alternate in -> scratch -> out -> scratch -> out ...; where their number is odd a device copy scratch -> out follows
+ *   the last, so the result is in values_out for every count; iterations == 0 is a device copy.  values_out == values_in is
+ *   allowed; otherwise the two must not overlap, and scratch must overlap neither.
+ * tn_mesh_scalar_gradient: the gradient of the piecewise linear interpolant of `values`, per face and per vertex.
+ *   face t is loaded as tn_mesh_regions loads it: VALID, the indices distinct, e1 = sub(p1, p0), e2 = sub(p2, p0), the face vector
+ *   n = e1 x e2 = (sub(mul(e1y, e2z), mul(e1z, e2y)), sub(mul(e1z, e2x), mul(e1x, e2z)), sub(mul(e1x, e2y), mul(e1y, e2x))) and
+ *   n2 = add(add(mul(nx, nx), mul(ny, ny)), mul(nz, nz)), all in fp64.
+ *     USABLE    valid, the indices distinct, all nine coordinates finite, the three values u0 u1 u2 finite, n2 > 0 and n2 < +inf.
+ *     g         a = sub((double)u1, (double)u0), b = sub((double)u2, (double)u0); A = e2 x n and B = n x e1, every component
+ *               sub(mul, mul) in the component order of n above (Ax = sub(mul(e2y, nz), mul(e2z, ny)), Bx = sub(mul(ny, e1z),
+ *               mul(nz, e1y)), ...); g_c = div(add(mul(a, A_c), mul(b, B_c)), n2).  In exact arithmetic g . e1 = u1 - u0,
+ *               g . e2 = u2 - u0 and g . n = 0.
+ *     |x|       of a vector x: sqrt(add(add(mul(xx, xx), mul(xy, xy)), mul(xz, xz)))
+ *     w         sqrt(n2), twice the area
+ *   face_gradient (double [T, 3], may be NULL): g of a usable face; the row of every other face is three times the NaN
+ *               0x7ff8000000000000.
+ *   vertex_gradient (float [V, 3]), vertex_magnitude (float [V]), one thread per vertex: S = (+0.0, +0.0, +0.0), W = +0.0; for
+ *               the corners of v's list in list order (a corner outside [0, 3T) is skipped) whose face is usable: S_c = add(S_c,
+ *               mul(w, g_c)), W = add(W, w).  (A face is listed once per corner, and a usable face has no repeated index.)  With no
+ *               usable face: the NaN 0x7fc00000 in all four floats.  Otherwise G_c = div(S_c, W), vertex_gradient[v] = (float)G_c
+ *               and vertex_magnitude[v] = (float)|G|.
+ *   totals (double [4], OVERWRITTEN): [0] the number of usable faces, [1] SUM2(w_f), [2] SUM2(mul(w_f, |g_f|)), [3] the largest
+ *               |g_f| of a usable face, +0.0 if there is none.  SUM2 is the ordered sum of tn_mesh_regions over the list of ALL T
+ *               faces in ascending face index — consecutive blocks of 256 faces, each accumulated from +0.0, then the block sums
+ *               from +0.0 in block order — in which a face that is not usable stands for +0.0.  [2] / [1] is the area-weighted
+ *               mean of |g|.  T == 0: all four are +0.0 (a memset).
+ *   How: one thread per face writes the row and a 32-byte record (w, w |g|, |g|, 1); one thread per vertex walks its list and
+ *   recomputes the gradient of each corner's face from the positions and the values (measured against reading the rows back:
+ *   profiles/micro/mesh_gradient.txt); one thread per 256 faces joins their records, one thread the partials.  workspace:
+ *   tn_mesh_scalar_gradient_workspace_bytes(V, T) device bytes, 8-byte aligned (the records and the partials); 0 for counts out of
+ *   range, positive otherwise.
+ * The kernels check what they dereference (a list is clipped to [0, 3T], a corner outside it or of an invalid triangle is skipped, a
+ * vertex is read only where the face's indices allow it), so a foreign index gives other numbers, never an access outside the arrays.
+ * All launches are plain, 256-thread blocks on `stream`; no allocation, no host synchronisation, no float atomics, and no block
+ * ever waits for another.
+ * TN_ERR_NULL: a required pointer is NULL (tn_mesh_scalar_smooth, with V > 0: values_in, offsets, values_out, with T > 0 triangles
+ * and corners, scratch with iterations > 0; tn_mesh_scalar_gradient: totals always; with V > 0 positions, values, offsets,
+ * vertex_gradient, vertex_magnitude; with T > 0 triangles and the workspace; with V > 0 and T > 0 corners); TN_ERR_SHAPE: V < 0 or
+ * > 2^31 - 1, T < 0 or 3T > 2^31 - 1, iterations < 0 or > 2^30 - 1, a float / int32 pointer not 4-byte aligned, face_gradient /
+ * totals / workspace not 8-byte aligned, buffers of tn_mesh_scalar_smooth that overlap; TN_ERR_UNSUPPORTED: lambda or mu not finite;
+ * TN_ERR_WORKSPACE: workspace_bytes too small (with T > 0).  All are returned before any launch.  tn_mesh_scalar_smooth with
+ * V == 0: TN_OK, nothing is launched.  tn_mesh_scalar_gradient: the faces and the totals are launched with T > 0 (V == 0: no face
+ * is usable), the vertices with V > 0 (T == 0: every vertex gets the NaN). */
+int tn_mesh_scalar_smooth(const float *values_in, const int32_t *triangles, int64_t num_triangles, int64_t num_vertices,
+                          const int32_t *offsets, const int32_t *corners, int32_t iterations, float lambda, float mu, int32_t fill,
+                          float *values_out, float *scratch, void *stream);
+size_t tn_mesh_scalar_gradient_workspace_bytes(int64_t num_vertices, int64_t num_triangles);
+int tn_mesh_scalar_gradient(const float *positions, const float *values, const int32_t *triangles, int64_t num_triangles,
+                            int64_t num_vertices, const int32_t *offsets, const int32_t *corners, double *face_gradient,
+                            float *vertex_gradient, float *vertex_magnitude, double *totals, void *workspace, size_t workspace_bytes,
+                            void *stream);
+
 /* A stable sort of n (uint64 key, int32 value) pairs on the device: a least-significant-digit radix sort, 8 bits per pass.
  *   The ORDERING BITS of a key are its low 8 * ceil(key_bits / 8) bits.  keys_out / values_out hold the input pairs in ascending
  *   order of their ordering bits; pairs whose ordering bits are equal keep their input order (the sort is stable).  Higher key

@@ -1,8 +1,9 @@
 // SUM2 over groups of faces, the one place for it (tn_mesh_regions.hip: the thermal regions; tn_mesh_patches.hip: the planar patches,
-// twice): every face carries a record, every face of a group the same label, and the group's row is its faces' records joined in
-// ascending face index, 256 at a time and then the 256-blocks' partials in block order — the order include/thermonerf_hip.h defines.
+// twice; tn_mesh_gradient.hip takes load_face and join_run alone, for its sums over all faces): every face carries a record, every
+// face of a group the same label, and the group's row is its faces' records joined in ascending face index, 256 at a time and then
+// the 256-blocks' partials in block order — the order include/thermonerf_hip.h defines.
 //
-//   load_face(...)                         one face's indices, corners and temperatures: what is valid, the cross product, the area,
+//   load_face(...)                         one face's indices, corners and temperatures: what is valid, the edges, the cross product, the area,
 //                                          area x centroid, the box, the face temperature — in this operation order only
 //   R                                      a record: static R empty(), void join(const R &r) with "r behind everything this holds", and
 //                                          kAhead, the records a walk loads ahead of its joins.  The ordered sums take one rounded
@@ -50,7 +51,8 @@ struct Face {
     bool placed;         // the indices distinct and inside [0, V), the nine coordinates finite: everything below `tf` is computed
     bool warm;           // the indices as above, the three temperatures finite: tf is computed
     float tf;            // the face temperature: the mean of the three, rounded once
-    double cr[3], n2;    // (p1 - p0) x (p2 - p0), its squared length
+    double e1[3], e2[3];  // p1 - p0, p2 - p0
+    double cr[3], n2;    // e1 x e2, its squared length
     double len, area;    // sqrt(n2), half of it
     double moment[3];    // area x centroid
     float lo[3], hi[3];  // the box of the corners
@@ -77,7 +79,7 @@ __device__ __forceinline__ Face load_face(const float *__restrict__ positions, c
     }
     if (f.warm) f.tf = (float)__ddiv_rn(__dadd_rn(__dadd_rn((double)f.c[0], (double)f.c[1]), (double)f.c[2]), 3.0);
     if (!f.placed) return f;
-    double e1[3], e2[3];
+    double *e1 = f.e1, *e2 = f.e2;
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
         e1[k] = __dsub_rn((double)f.p[1][k], (double)f.p[0][k]);

@@ -26,25 +26,13 @@
 #include <cmath>
 
 #include "tn_device.h"
+#include "tn_mesh_lists.h"
 
 using namespace tn;
 
 namespace {
 
 constexpr int kTile = 256;  // corners / vertices per block of every kernel here (tn_mesh_tile())
-
-struct Tri {
-    int v[3];
-};
-
-__device__ __forceinline__ Tri load_triangle(const int *__restrict__ tri, long long t) {
-    return *reinterpret_cast<const Tri *>(tri + 3 * t);  // 12 bytes, 4-byte aligned: one global_load_dwordx3
-}
-
-__device__ __forceinline__ bool valid_triangle(const Tri &t, int num_vertices) {
-    const unsigned n = (unsigned)num_vertices;
-    return (unsigned)t.v[0] < n && (unsigned)t.v[1] < n && (unsigned)t.v[2] < n;
-}
 
 struct Vec {
     float x, y, z;
@@ -83,14 +71,6 @@ offsets_kernel(const unsigned long long *__restrict__ sorted_keys, long long num
         if (sorted_keys[mid] < (unsigned long long)v) lo = mid + 1; else hi = mid;
     }
     offsets[v] = (int)lo;  // <= 3T <= 2^31 - 1
-}
-
-// the list of vertex v, clipped to the corners that exist
-__device__ __forceinline__ void list_of(const int *__restrict__ offsets, long long v, long long num_corners, long long &begin,
-                                        long long &end) {
-    begin = offsets[v], end = offsets[v + 1];
-    begin = begin < 0 ? 0 : begin;
-    end = end > num_corners ? num_corners : end;
 }
 
 __global__ void __launch_bounds__(kTile)
@@ -166,22 +146,6 @@ inline int bit_length(unsigned long long x) {
     int bits = 0;
     for (; x; x >>= 1) ++bits;
     return bits;
-}
-
-inline bool overlap(const void *a, const void *b, size_t bytes) {
-    const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
-    return x < y + bytes && y < x + bytes;
-}
-
-// what the two per-vertex entries share: TN_OK, or the code of the first argument that is wrong
-inline int check_indexed_mesh(const float *positions, const int32_t *triangles, int64_t num_triangles, int64_t num_vertices,
-                              const int32_t *offsets, const int32_t *corners, const float *out) {
-    if (num_vertices > 0 && (!positions || !offsets || !out)) return TN_ERR_NULL;
-    if (num_vertices > 0 && num_triangles > 0 && (!triangles || !corners)) return TN_ERR_NULL;
-    if (bad_mesh(num_vertices, num_triangles)) return TN_ERR_SHAPE;
-    if (misaligned(positions, 4) || misaligned(triangles, 4) || misaligned(offsets, 4) || misaligned(corners, 4) || misaligned(out, 4))
-        return TN_ERR_SHAPE;
-    return TN_OK;
 }
 
 }  // namespace
