@@ -12,7 +12,9 @@ kernels above them (tn_ray_render_bwd, tn_weights_bwd, tn_composite_bwd, the dis
 held element by element to tests/ray_losses_reference.py by tests/test_gpu_ray_losses.py: exact on dyadic and single-interval
 inputs, bounded by counted roundings elsewhere.  The forward half of that chain (tn_sample_pdf, tn_weights_fwd, tn_composite_fwd,
 tn_depth_fwd, tn_sample_initial, the frustum kernels, tn_ray_render_fwd / tn_ray_render_depth_fwd against the modular calls) is held
-the same way to tests/ray_forward_reference.py by tests/test_gpu_ray_forward.py."""
+the same way to tests/ray_forward_reference.py by tests/test_gpu_ray_forward.py.  The MLP stage between them (tn_linear_fwd / _bwd /
+_chain_bwd, tn_field_bwd_fused in its three forms, tn_ray_head_fwd / _bwd, tn_density_fwd_train / _bwd_train) is held entry by entry to
+tests/mlp_reference.py by tests/test_gpu_mlp.py, second rounds of the persistent blocks and the VALU backward included."""
 import copy
 import ctypes as C
 

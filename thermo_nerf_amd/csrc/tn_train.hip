@@ -601,7 +601,7 @@ template <int NI>
 __global__ void __launch_bounds__(kBlock)
 linear_bwd_kernel(const float *__restrict__ x, int ldx, const float *__restrict__ y, const float *__restrict__ dy, int ldy,
                   const float *__restrict__ W, int IN, int OUT, int act, long long n, float *__restrict__ dx, int lddx,
-                  int accumulate_dx, float *__restrict__ dW, float *__restrict__ db, float *__restrict__ partials) {
+                  int accumulate_dx, float *__restrict__ dW, float *__restrict__ db) {
     constexpr int INP = 4 * NI;
     __shared__ __attribute__((aligned(16))) float Ws[64 * INP];  // [o][i], zero padded
     __shared__ float gs[TILE * LDP];                               // g = dy * act'(y)   [row][o]
@@ -667,22 +667,15 @@ linear_bwd_kernel(const float *__restrict__ x, int ldx, const float *__restrict_
             }
         }
     }
-    if (want_w && lane < OUT) {
-        if (partials) {  // [block][i (INP rows) | bias row][64]: plain coalesced stores, summed by linear_bwd_reduce_kernel
-            float *pb = partials + (size_t)blockIdx.x * (INP + 1) * 64;
+    if (want_w && lane < OUT) {  // one atomic per block and entry (the form with the slabs is linear_bwd_mfma_kernel)
+        if (dW) {
 #pragma unroll
-            for (int k = 0; k < NI; ++k) pb[(grp * NI + k) * 64 + lane] = accw[k];
-            if (grp == 0) pb[INP * 64 + lane] = accb;
-        } else {
-            if (dW) {
-#pragma unroll
-                for (int k = 0; k < NI; ++k) {
-                    const int i = grp * NI + k;
-                    if (i < IN) atomic_add_f32(dW + lane * IN + i, accw[k]);
-                }
+            for (int k = 0; k < NI; ++k) {
+                const int i = grp * NI + k;
+                if (i < IN) atomic_add_f32(dW + lane * IN + i, accw[k]);
             }
-            if (db && grp == 0) atomic_add_f32(db + lane, accb);
         }
+        if (db && grp == 0) atomic_add_f32(db + lane, accb);
     }
 }
 
@@ -2330,7 +2323,6 @@ int tn_linear_bwd(const float *x, int32_t ldx, const float *y, const float *dy, 
     const int blocks = grid_for((n + TILE - 1) / TILE, 1, kLinBwdBlocks);
     const dim3 g(blocks), b(kBlock);
     hipStream_t st = (hipStream_t)stream;
-    const int INP = IN <= 16 ? 16 : IN <= 32 ? 32 : 64;
     const bool want_w = d_weight || d_bias;
     float *partials = nullptr;
     if (want_w && workspace && workspace_bytes >= (size_t)blocks * 65 * 64 * sizeof(float))
@@ -2366,19 +2358,14 @@ int tn_linear_bwd(const float *x, int32_t ldx, const float *y, const float *dy, 
     }
     if (IN <= 16)
         hipLaunchKernelGGL(linear_bwd_kernel<4>, g, b, 0, st, x, ldx, y, dy, ldy, lin->weight, IN, OUT, act, (long long)n, dx,
-                           lddx, accumulate_dx, d_weight, d_bias, partials);
+                           lddx, accumulate_dx, d_weight, d_bias);
     else if (IN <= 32)
         hipLaunchKernelGGL(linear_bwd_kernel<8>, g, b, 0, st, x, ldx, y, dy, ldy, lin->weight, IN, OUT, act, (long long)n, dx,
-                           lddx, accumulate_dx, d_weight, d_bias, partials);
+                           lddx, accumulate_dx, d_weight, d_bias);
     else
         hipLaunchKernelGGL(linear_bwd_kernel<16>, g, b, 0, st, x, ldx, y, dy, ldy, lin->weight, IN, OUT, act, (long long)n, dx,
-                           lddx, accumulate_dx, d_weight, d_bias, partials);
+                           lddx, accumulate_dx, d_weight, d_bias);
     TN_LAUNCH_CHECK();
-    if (partials) {
-        hipLaunchKernelGGL(linear_bwd_reduce_kernel, dim3(INP + 1, kRedSplit), dim3(kBlock), 0, st, partials, blocks, INP, IN, OUT,
-                           d_weight, IN, d_bias);
-        TN_LAUNCH_CHECK();
-    }
     return TN_OK;
 }
 
