@@ -4,7 +4,17 @@
 //   expf(-t):   t in [0, 87] (results normal), relative error in units of 2^-24; t in (87, 104] (results denormal or zero),
 //               absolute error in units of 2^-126 (one smallest normal)
 //   log10f(x):  x in [2^-24, 2^40], relative error in units of 2^-24
+// and of the three fast operations of the eval field kernels, for which the platform documents no bound (tests/field_eval_reference.py
+// takes K_FEXP_A / K_FEXP_B, K_FSIG and K_FSIG_PRE from the output, again with a margin of 2x):
+//   __expf(x):  x in [-87, 0] and in [-30, 30], relative error in units of 2^-24 as a + b |x| (v_exp_f32 of the ROUNDED product
+//               x log2(e) loses with |x|): a = the worst error over |x| <= 1, b = the largest (error - a) / |x| beyond;
+//               x in [-104, -87): absolute error in units of 2^-126
+//   fast_sigmoid(x) = v_rcp(1 + __expf(-x)) and fast_sigmoid_prescaled(a) = v_rcp(1 + v_exp(a)) (a = -log2(e) x, given as fp32):
+//               x in [-100, 100] / a in [-144, 144], absolute error in units of 2^-24 against 1 / (1 + e^-x) and 1 / (1 + 2^a)
 // Each range: N points on a regular grid plus N pseudo-random ones, and the powers of two inside it.
+// The flags are the library's (thermo_nerf_amd/csrc/Makefile: -O3 -ffp-contract=off, no fast-math, default denormal mode), under which
+// __expf(x) compiles to v_mul_f32 x, 0x3fb8aa3b + v_exp_f32 and the two sigmoids to that plus v_add_f32 and v_rcp_f32, in this tool
+// as in the library's kernels: the constants describe the same instruction sequences.
 //   hipcc --offload-arch=gfx950 -O3 -ffp-contract=off tools/micro/libm_accuracy.hip -o tools/micro/libm_accuracy_bin
 #include <hip/hip_runtime.h>
 #include <cmath>
@@ -17,7 +27,13 @@
 __global__ void __launch_bounds__(256) apply(const float *x, float *y, int n, int fn) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    y[i] = fn == 0 ? expf(-x[i]) : log10f(x[i]);
+    const float v = x[i];
+    y[i] = fn == 0   ? expf(-v)
+           : fn == 1 ? log10f(v)
+           : fn == 2 ? __expf(v)
+           : fn == 3 ? __builtin_amdgcn_rcpf(1.0f + __expf(-v))
+           : fn == 4 ? __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(v))
+                     : __builtin_amdgcn_rcpf(v);
 }
 
 static std::vector<float> device(const std::vector<float> &x, int fn) {
@@ -91,6 +107,56 @@ int main() {
         }
         printf("log10f(x) x in [2^-24, 2^40] %zu points  worst relative error %.4f x 2^-24 at x = %.9g\n", x.size(), worst, at);
         printf("log10f(x) same points: worst |error| / (2^-24 max(|log10 x|, 1)) = %.4f\n", worst_abs);
+    }
+    const int M = 5000000;  // 10^7 arguments a range
+    {
+        std::vector<float> x = points(-87.0, 0.0, M, false);
+        const std::vector<float> x2 = points(-30.0, 30.0, M, false);
+        x.insert(x.end(), x2.begin(), x2.end());
+        const std::vector<float> y = device(x, 2);
+        double a = 0.0, b = 0.0, worst = 0.0, at = 0.0;
+        for (size_t i = 0; i < x.size(); ++i) {
+            const double want = exp((double)x[i]), e = fabs((double)y[i] - want) / (u24 * want);
+            if (e > worst) worst = e, at = x[i];
+            if (fabs(x[i]) <= 1.0f) a = fmax(a, e);
+        }
+        for (size_t i = 0; i < x.size(); ++i) {
+            const double want = exp((double)x[i]), e = fabs((double)y[i] - want) / (u24 * want);
+            if (fabs(x[i]) > 1.0f) b = fmax(b, (e - a) / fabs((double)x[i]));
+        }
+        printf("__expf(x)  x in [-87, 0] and [-30, 30]  %zu points  worst relative error %.4f x 2^-24 at x = %.9g;  as a + b |x|: a = %.4f, b = %.4f\n",
+               x.size(), worst, at, a, b);
+    }
+    {
+        const std::vector<float> x = points(-104.0, -87.0, M / 4, false), y = device(x, 2);
+        double worst = 0.0, at = 0.0;
+        for (size_t i = 0; i < x.size(); ++i) {
+            if (x[i] >= -87.0f) continue;
+            const double e = fabs((double)y[i] - exp((double)x[i])) / tiny;
+            if (e > worst) worst = e, at = x[i];
+        }
+        printf("__expf(x)  x in [-104, -87)  %zu points  worst absolute error %.4f x 2^-126 at x = %.9g\n", x.size(), worst, at);
+    }
+    for (int fn = 3; fn <= 4; ++fn) {
+        const double span = fn == 3 ? 100.0 : 144.0;
+        const std::vector<float> x = points(-span, span, M, false), y = device(x, fn);
+        double worst = 0.0, at = 0.0;
+        for (size_t i = 0; i < x.size(); ++i) {
+            const double want = fn == 3 ? 1.0 / (1.0 + exp(-(double)x[i])) : 1.0 / (1.0 + exp2((double)x[i]));
+            const double e = fabs((double)y[i] - want) / u24;
+            if (!(e <= worst)) worst = e, at = x[i];
+        }
+        printf("%s in [-%g, %g]  %zu points  worst absolute error %.4f x 2^-24 at %.9g\n",
+               fn == 3 ? "fast_sigmoid(x) = v_rcp(1 + __expf(-x))  x" : "fast_sigmoid_prescaled(a) = v_rcp(1 + v_exp(a))  a", span, span, x.size(), worst, at);
+    }
+    {   // v_rcp_f32 alone: the FAST kernels' 1 / x in spacing_fn_inv and in the scene contraction (K_RCP)
+        const std::vector<float> x = points(ldexp(1.0, -20), ldexp(1.0, 20), M, true), y = device(x, 5);
+        double worst = 0.0, at = 0.0;
+        for (size_t i = 0; i < x.size(); ++i) {
+            const double want = 1.0 / (double)x[i], e = fabs((double)y[i] - want) / (u24 * want);
+            if (e > worst) worst = e, at = x[i];
+        }
+        printf("v_rcp_f32(x)  x in [2^-20, 2^20]  %zu points  worst relative error %.4f x 2^-24 at x = %.9g\n", x.size(), worst, at);
     }
     return 0;
 }
