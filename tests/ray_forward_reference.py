@@ -295,8 +295,10 @@ def draws_fp32(u, u_rand, R: int, n_out: int, per_sample: bool, fault: Optional[
 
 
 def sample_pdf(weights, existing_bins, u, u_rand, nears, fars, n_out: int, lin: bool, per_sample: bool,
-               cdf_fp32: bool = False) -> PdfRef:
-    """spacing bins of tn_sample_pdf in fp64 (nears / fars / lin only enter the euclidean map, see the module docstring)"""
+               cdf_fp32: bool = False, k: Optional[float] = None, k_t: float = 5.0) -> PdfRef:
+    """spacing bins of tn_sample_pdf in fp64 (nears / fars / lin only enter the euclidean map, see the module docstring).
+    k, k_t: the CDF count and the count of t and its product of ANOTHER kernel that resamples the same way (the fused proposal
+    pass, tests/proposal_eval_reference.py); by default those of sample_pdf_kernel, k_cdf(n_in) and 5"""
     w, ex = _c(weights), _c(existing_bins).astype(f64)
     R, n_in = w.shape
     wpad = (w + f32(0.01)).astype(f32).astype(f64)
@@ -316,14 +318,14 @@ def sample_pdf(weights, existing_bins, u, u_rand, nears, fars, n_out: int, lin: 
         b = b0 + t * (b1 - b0)
         dc, db = np.diff(cdf, axis=1), np.abs(np.diff(ex, axis=1))
         slope = np.where(dc > 0, db / np.where(dc > 0, dc, 1.0), np.where(db > 0, np.inf, 0.0))
-    d = k_cdf(n_in) * EPS32
+    d = (k_cdf(n_in) if k is None else k) * EPS32
     tol = np.zeros_like(b)
     for r in range(R):
         klo = np.clip(np.searchsorted(cdf[r, 1:], uu[r] - d, side="left"), 0, n_in - 1)
         khi = np.maximum(np.clip(np.searchsorted(cdf[r, :-1], uu[r] + d, side="right") - 1, 0, n_in - 1), klo)
         for j in range(uu.shape[1]):
             lo, hi = int(klo[j]), int(khi[j]) + 1
-            tol[r, j] = d * slope[r, lo:hi].max() + EPS32 * (5 * db[r, lo:hi].max() + np.abs(ex[r, lo:hi + 1]).max())
+            tol[r, j] = d * slope[r, lo:hi].max() + EPS32 * (k_t * db[r, lo:hi].max() + np.abs(ex[r, lo:hi + 1]).max())
     return PdfRef(b, tol + TINY32, cdf, uu, idx)
 
 

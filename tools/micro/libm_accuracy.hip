@@ -11,6 +11,8 @@
 //               x in [-104, -87): absolute error in units of 2^-126
 //   fast_sigmoid(x) = v_rcp(1 + __expf(-x)) and fast_sigmoid_prescaled(a) = v_rcp(1 + v_exp(a)) (a = -log2(e) x, given as fp32):
 //               x in [-100, 100] / a in [-144, 144], absolute error in units of 2^-24 against 1 / (1 + e^-x) and 1 / (1 + 2^a)
+// and of powf(w, a), w in [0, 1], a in {0.5, 0.75}: the annealed PDF resampling of the fused proposal pass (tests/proposal_eval_reference.py
+// takes K_POW from it the same way): relative error in units of 2^-24, 0 and 1 required exact
 // Each range: N points on a regular grid plus N pseudo-random ones, and the powers of two inside it.
 // The flags are the library's (thermo_nerf_amd/csrc/Makefile: -O3 -ffp-contract=off, no fast-math, default denormal mode), under which
 // __expf(x) compiles to v_mul_f32 x, 0x3fb8aa3b + v_exp_f32 and the two sigmoids to that plus v_add_f32 and v_rcp_f32, in this tool
@@ -24,7 +26,7 @@
 
 #define CK(x) do { hipError_t e = (x); if (e != hipSuccess) { printf("%s: %s\n", #x, hipGetErrorString(e)); exit(1); } } while (0)
 
-__global__ void __launch_bounds__(256) apply(const float *x, float *y, int n, int fn) {
+__global__ void __launch_bounds__(256) apply(const float *x, float *y, int n, int fn, float a) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     const float v = x[i];
@@ -33,16 +35,17 @@ __global__ void __launch_bounds__(256) apply(const float *x, float *y, int n, in
            : fn == 2 ? __expf(v)
            : fn == 3 ? __builtin_amdgcn_rcpf(1.0f + __expf(-v))
            : fn == 4 ? __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(v))
-                     : __builtin_amdgcn_rcpf(v);
+           : fn == 5 ? __builtin_amdgcn_rcpf(v)
+                     : powf(v, a);  // a run-time exponent, as the kernels' pdf_anneal is: the library's general powf
 }
 
-static std::vector<float> device(const std::vector<float> &x, int fn) {
+static std::vector<float> device(const std::vector<float> &x, int fn, float a = 0.0f) {
     const int n = (int)x.size();
     float *dx, *dy;
     CK(hipMalloc(&dx, n * sizeof(float)));
     CK(hipMalloc(&dy, n * sizeof(float)));
     CK(hipMemcpy(dx, x.data(), n * sizeof(float), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(apply, dim3((n + 255) / 256), dim3(256), 0, 0, dx, dy, n, fn);
+    hipLaunchKernelGGL(apply, dim3((n + 255) / 256), dim3(256), 0, 0, dx, dy, n, fn, a);
     CK(hipGetLastError());
     std::vector<float> y(n);
     CK(hipMemcpy(y.data(), dy, n * sizeof(float), hipMemcpyDeviceToHost));
@@ -157,6 +160,26 @@ int main() {
             if (e > worst) worst = e, at = x[i];
         }
         printf("v_rcp_f32(x)  x in [2^-20, 2^20]  %zu points  worst relative error %.4f x 2^-24 at x = %.9g\n", x.size(), worst, at);
+    }
+    {   // powf(w, a): the PDF resampling of an annealed proposal pass (pdf_anneal != 1) raises a weight in [0, 1] to a in (0, 1)
+        std::vector<float> x = points(0.0, 1.0, M / 2, false);
+        const std::vector<float> x2 = points(ldexp(1.0, -60), 1.0, M / 2, true);
+        x.insert(x.end(), x2.begin(), x2.end());
+        x.push_back(0.0f);
+        x.push_back(1.0f);
+        double worst_all = 0.0;
+        for (const double a : {0.5, 0.75}) {
+            const std::vector<float> y = device(x, 6, (float)a);
+            double worst = 0.0, at = 0.0;
+            for (size_t i = 0; i < x.size(); ++i) {
+                const double want = pow((double)x[i], a);
+                const double e = want == 0.0 ? (y[i] == 0.0f ? 0.0 : INFINITY) : fabs((double)y[i] - want) / (u24 * want);
+                if (!(e <= worst)) worst = e, at = x[i];
+            }
+            worst_all = fmax(worst_all, worst);
+            printf("powf(w, %.2f)  w in [0, 1]  %zu points  worst relative error %.4f x 2^-24 at w = %.9g\n", a, x.size(), worst, at);
+        }
+        printf("powf(w, a)  a in {0.5, 0.75}: the worst of both %.4f x 2^-24\n", worst_all);
     }
     return 0;
 }
