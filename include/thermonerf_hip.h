@@ -1422,6 +1422,121 @@ int tn_mesh_patches(const float *positions, const float *temperature, const int3
                     int64_t num_triangles, const int32_t *twin, double min_cos, tn_mesh_patch *patches, int64_t capacity_patches,
                     int32_t *face_patch, int64_t *counts, double *totals, void *workspace, size_t workspace_bytes, void *stream);
 
+/* Thermal hot spots of an indexed triangle list: the local maxima of the per-vertex temperature, their basins, the saddles between
+ * adjacent basins, the 0-dimensional persistence of the basins (every peak's prominence in degrees) and, per spot that stands out, the
+ * extent and the row of a thermal region.  Cold spots are the same with the order reversed.  temperature [V] floats, triangles [T, 3]
+ * int32, V = num_vertices, T = num_triangles; offsets / corners are tn_mesh_incidence's of the SAME triangles and V.  Every output is
+ * defined to the bit, and all but the rows' floats are integers.
+ *   ORDER       a vertex is FINITE if its temperature is neither a NaN nor infinite.  HOT order (coldest == 0): u is ABOVE v iff
+ *               T[u] > T[v] compared as numbers (-0.0 == +0.0), or T[u] == T[v] and u < v.  With coldest != 0 the comparison of the
+ *               temperatures is reversed, the tie rule is not.  rank[v] (int32 [V]) is v's position in that order, 0 the top; the
+ *               vertices that are not finite follow all finite ones in ascending index.  It is one tn_sort_pairs of (key, 0 .. V-1)
+ *               over 32 key bits: with k the monotone 32-bit key of the float (-0.0 taken as +0.0; the sign bit set for a positive
+ *               float, all bits flipped for a negative one) the key is ~k for HOT, k for COLD and 0xffffffff for a vertex that is
+ *               not finite — finite floats have k and ~k in [0x00800000, 0xff7fffff].  Everything below compares ranks, never floats.
+ *   NEIGHBOURS  of a finite vertex v: the finite vertices t[(j + 1) % 3] and t[(j + 2) % 3], where they differ from v, over the
+ *               corners (t, j) of v's list — clipped and checked as tn_mesh_scalar_smooth does it, VALID triangles only (all three
+ *               indices in [0, V)).  A vertex that is not finite is nobody's neighbour and belongs to nothing: -1 in vertex_basin.
+ *   ASCENT      up[v] = the neighbour of the smallest rank if that rank is below rank[v], else v itself: v is then a PEAK.  peak[v] is
+ *               the fixed point of up, reached by pointer jumping in ceil(log2(max(2, V))) launches over two arrays, each launch
+ *               reading one and writing the other.
+ *   BASINS      numbered b = 0 .. B-1 in ascending peak vertex (count / scan / emit over the peak flags).  vertex_basin (int32 [V],
+ *               always fully written): b, or -1.  basin_peak (int32, capacity_basins rows): the peak vertex of basin b.
+ *   SADDLES     for every half-edge (u, w) = (t[j], t[(j + 1) % 3]) of a valid triangle with both ends finite and vertex_basin[u] = a
+ *               != vertex_basin[w] = b, the edge's PASS is max(rank[u], rank[w]): its lower end.  The saddle of the unordered pair
+ *               {a, b} is the smallest pass over all half-edges between them.  saddles (tn_mesh_saddle, capacity_saddles rows): one
+ *               row per adjacent pair in ascending (a, b) with a < b: the pair, pass_vertex (the vertex of that rank) and pass_rank.
+ *   counts (device int64 [3], OVERWRITTEN): [0] B and [1] S, the number of adjacent pairs — the FULL numbers; rows at or beyond a
+ *               capacity are not written (capacity 0 with a NULL table: the sizing call) —, [2] the finite vertices.
+ * tn_mesh_peaks, how: the keys and the sort; one thread per rank writes rank[v]; one thread per vertex walks its list (a minimum over
+ * integers is order-free); the jumps; count, one-block scan, emit over the peak flags; one thread per half-edge writes the key
+ * (min(a, b), max(a, b)) in 2 bit_length(V) bits, or the key of no pair; tn_sort_pairs puts a pair's half-edges side by side and the
+ * pairs in order; count / scan / emit over the heads of the runs, and the head's thread walks its run for the smallest pass.
+ * workspace: tn_mesh_peaks_workspace_bytes(V, T) device bytes, 8-byte aligned; 0 for counts out of range.  V == 0: counts is zeroed by a
+ * memset, nothing is launched.  T == 0: every finite vertex is a peak, S = 0, the saddle steps are not launched.
+ * TN_ERR_NULL: counts is NULL; with V > 0 temperature, offsets, rank, vertex_basin or the workspace; with V > 0 and T > 0 triangles or
+ * corners; basin_peak / saddles with a capacity > 0; TN_ERR_SHAPE: V < 0 or > 2^31 - 1, T < 0 or 3T > 2^31 - 1, a negative capacity, a
+ * float / int32 pointer or saddles not 4-byte aligned, counts / workspace not 8-byte aligned; TN_ERR_WORKSPACE: workspace_bytes too
+ * small (with V > 0).  All are returned before any launch, in the order of the code: counts, the shape, the other pointers, the
+ * alignment, the workspace.
+ *
+ * tn_basin_persistence, ON THE HOST, every pointer a HOST pointer, integers only: basin_rank (int32 [B]) = rank[basin_peak[b]];
+ * saddles [S] as above, in the table's order.  The saddles are taken in ascending pass_rank; all saddles of one pass_rank are a BATCH,
+ * taken in ascending row.  A union-find over the basins keeps as a component's representative the member with the smallest peak rank.
+ * A saddle that joins two different components kills the representative with the larger peak rank: death_saddle[it] = the row.  After
+ * the batch parent[d] = find(d) for every basin d that died in it: the eldest of everything joined at that pass vertex.  A basin that
+ * never dies keeps death_saddle = parent = -1: there is one per connected component of the finite graph.  death_saddle, parent: int32
+ * [B], fully written.  It allocates its two index arrays (S + B ints) and nothing else; O(S log S).
+ * TN_ERR_SHAPE: B or S negative or > 2^31 - 1, a pointer not 4-byte aligned; TN_ERR_NULL: basin_rank, death_saddle or parent with
+ * B > 0, saddles with S > 0; TN_ERR_UNSUPPORTED: a row names a basin outside [0, B) or one basin twice (nothing is written);
+ * TN_ERR_WORKSPACE: the two arrays could not be allocated.
+ * The PROMINENCE of basin b is (float)sub((double)T[peak], (double)T[pass_vertex]) of its death saddle — the operands swapped for
+ * coldest —, +inf for a basin that never dies; the caller computes it.
+ *
+ * tn_mesh_spots: the caller has chosen the K spots (the basins whose prominence exceeds its threshold, every other basin joined to the
+ * first survivor on its parent chain) and uploads basin_spot (int32 [B]: the spot k of every basin, -1 of a basin in none), and per
+ * spot spot_peak (the peak vertex), spot_limit (int32: pass_rank of the spot's own death saddle; any value >= V for a spot that never
+ * dies) and spot_bound (float: (float)sub((double)T[peak], (double)extent_drop) for HOT, (float)add(...) for COLD; -inf / +inf for no
+ * drop).  rank and vertex_basin are tn_mesh_peaks' of the same temperature and order.
+ *   EXTENT of spot k: the finite vertices v with vertex_basin[v] = b in [0, B), basin_spot[b] = k in [0, K), rank[v] < spot_limit[k]
+ *               — strictly above the spot's saddle — and T[v] >= spot_bound[k] (coldest != 0: T[v] <= spot_bound[k]), compared in
+ *               fp32.  The bound is "the spot within X degrees of its peak"; connectivity is NOT re-checked: with a bound the extent
+ *               may fall into several pieces, which stay one spot.
+ *   vertex_spot (int32 [V], always fully written): k or -1.
+ *   face_spot (int32 [T], always fully written): k iff face t is USABLE as tn_mesh_regions defines it and all three vertices lie in
+ *               the extent of k; -1 otherwise.
+ *   tn_mesh_spot, row k of `spots` (80 bytes, K rows, all written): the fields of tn_mesh_region over the spot's faces in ascending
+ *               face index, by the same definitions and the same SUM2 — area, faces, mean_temperature, centroid, min_temperature /
+ *               max_temperature, bounds, hottest_vertex / coldest_vertex (over the faces' vertices) —; label = spot_peak[k];
+ *               vertices = the number of vertices in the extent; reserved = 0.  A spot whose extent holds no whole face has area
+ *               +0.0, faces 0, hottest_vertex = coldest_vertex = -1 and the NaN 0x7fc00000 in every float; with faces of area 0
+ *               alone the mean and the centroid are that NaN, as in a region of area 0.
+ *   counts (device int64 [3], OVERWRITTEN): [0] the spots that have a face, [1] the faces that belong to a spot, [2] the usable faces.
+ * How: one thread per vertex writes vertex_spot and counts its spot's vertices (an integer atomic); one thread per face writes the
+ * 96-byte record of tn_mesh_regions, face_spot and the key; then the steps of tn_mesh_regions with the spot as the label: the two
+ * compacted lists, tn_sort_pairs of (spot, face), the heads, the 256-blocks, the partials; one thread per spot joins its partials.
+ * workspace: tn_mesh_spots_workspace_bytes(V, T, K) device bytes, 8-byte aligned; 0 for counts out of range or K > V.  V == 0: counts
+ * is zeroed and face_spot filled with -1 by memsets, nothing is launched.  T == 0: vertex_spot and the rows (all empty, with their
+ * vertex counts) are written.  K == 0: vertex_spot and face_spot are -1, counts[2] is still counted.
+ * TN_ERR_NULL: counts is NULL; with V > 0 positions, temperature, rank, vertex_basin, vertex_spot or the workspace; with T > 0
+ * triangles or face_spot; with B > 0 basin_spot; with K > 0 spot_peak, spot_limit, spot_bound or spots; TN_ERR_SHAPE: V or T out of
+ * range as above, B < 0 or > V, K < 0 or > B, a float / int32 pointer not 4-byte aligned, spots / counts / workspace not 8-byte
+ * aligned; TN_ERR_WORKSPACE: workspace_bytes too small (with V > 0).  All are returned before any launch, in the order of the code:
+ * counts, the shape, the other pointers, the alignment, the workspace.
+ * Both device entries launch plain 256-thread blocks (the scans: one block of 1024) on `stream` only: no allocation, no host
+ * synchronisation, no float atomics (the integer ones: counts[2] of tn_mesh_peaks, one per block; a spot's vertices; the sort's), no
+ * block waits for another.  The kernels check what they dereference — a list is clipped to [0, 3T], a corner outside it or of an
+ * invalid triangle is skipped, a rank, a basin, a spot and a sorted position are used only inside their arrays —, so a foreign index
+ * or table gives other numbers, never an access outside the arrays.  Inputs and outputs must not overlap. */
+typedef struct tn_mesh_saddle {
+    int32_t a, b;
+    int32_t pass_vertex, pass_rank;
+} tn_mesh_saddle;
+typedef struct tn_mesh_spot {
+    double area;
+    int32_t label;
+    int32_t faces;
+    float mean_temperature;
+    float min_temperature, max_temperature;
+    float centroid[3];
+    float bounds[6];
+    int32_t coldest_vertex, hottest_vertex;
+    int32_t vertices, reserved;
+} tn_mesh_spot;
+size_t tn_mesh_peaks_workspace_bytes(int64_t num_vertices, int64_t num_triangles);
+int tn_mesh_peaks(const float *temperature, const int32_t *triangles, int64_t num_triangles, int64_t num_vertices,
+                  const int32_t *offsets, const int32_t *corners, int32_t coldest, int32_t *rank, int32_t *vertex_basin,
+                  int32_t *basin_peak, int64_t capacity_basins, tn_mesh_saddle *saddles, int64_t capacity_saddles, int64_t *counts,
+                  void *workspace, size_t workspace_bytes, void *stream);
+int tn_basin_persistence(const int32_t *basin_rank, int64_t num_basins, const tn_mesh_saddle *saddles, int64_t num_saddles,
+                         int32_t *death_saddle, int32_t *parent);
+size_t tn_mesh_spots_workspace_bytes(int64_t num_vertices, int64_t num_triangles, int64_t num_spots);
+int tn_mesh_spots(const float *positions, const float *temperature, const int32_t *triangles, int64_t num_vertices,
+                  int64_t num_triangles, const int32_t *rank, const int32_t *vertex_basin, const int32_t *basin_spot, int64_t num_basins,
+                  const int32_t *spot_peak, const int32_t *spot_limit, const float *spot_bound, int64_t num_spots, int32_t coldest,
+                  int32_t *vertex_spot, int32_t *face_spot, tn_mesh_spot *spots, int64_t *counts, void *workspace,
+                  size_t workspace_bytes, void *stream);
+
 /* ------------------------------------------------------------------------------------------------------
  * Fused forward: Model.forward (collider) + ThermalNerfModel.get_outputs
  * [REF thermal_nerf_model.py:210-275]

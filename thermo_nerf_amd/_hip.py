@@ -339,6 +339,12 @@ SIGNATURES = {
     "tn_mesh_scalar_smooth": (C.c_int, [_vp, _vp, _i64, _i64, _vp, _vp, _i32, C.c_float, C.c_float, _i32, _vp, _vp, _vp]),
     "tn_mesh_scalar_gradient_workspace_bytes": (_sz, [_i64, _i64]),
     "tn_mesh_scalar_gradient": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "tn_mesh_peaks_workspace_bytes": (_sz, [_i64, _i64]),
+    "tn_mesh_peaks": (C.c_int, [_vp, _vp, _i64, _i64, _vp, _vp, _i32, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _sz, _vp]),
+    "tn_basin_persistence": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp]),
+    "tn_mesh_spots_workspace_bytes": (_sz, [_i64, _i64, _i64]),
+    "tn_mesh_spots": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp,
+                                _sz, _vp]),
     "tn_render_workspace_bytes": (_sz, [C.POINTER(tn_render_config), _i64]),
     "tn_render_rays_fwd": (
         C.c_int,

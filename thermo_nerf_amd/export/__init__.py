@@ -19,6 +19,8 @@
   area, flatness and degrees; the edge-connected components; the view that looks straight at a patch.
 - gradient.py: where the temperature changes fastest — the surface gradient in degrees per unit as a mesh of its own — and the
   NaN-aware smoothing of the degrees that comes first, which also fills the holes where nothing was measured.
+- hotspots.py: the hot and cold spots of a mesh by topological persistence: every peak's prominence in degrees against its own
+  surroundings, the extent of each spot that stands out and its area, mean temperature and location.
 - ply.py: their PLY files.  _common.py: the argument checks they share.  cli.py: what the command lines under tools/ share.
 """
 from .closest import ClosestPoints, MeshDifference, mesh_closest, mesh_closest_into, mesh_difference  # noqa: F401
@@ -26,6 +28,9 @@ from .components import (ComponentsInfo, MeshComponents, filter_components, mesh
                          mesh_components_workspace_bytes, remove_small_components)
 from .gradient import (MeshGradient, ScalarGradient, fill_temperature, mesh_scalar_gradient_workspace_bytes,  # noqa: F401
                        scalar_gradient, smooth_temperature, smooth_values, thermal_gradient)
+from .hotspots import (SADDLE_DTYPE, SPOT_BYTES, SPOT_DTYPE, BasinPersistence, MeshPeaks, ThermalHotspots,  # noqa: F401
+                       basin_persistence, choose_spots, merge_basins, mesh_peaks, mesh_peaks_workspace_bytes, mesh_spots,
+                       mesh_spots_workspace_bytes, prominence_of, spot_bounds, thermal_hotspots)
 from .isolines import (CURVE_DTYPE, MeshCurves, MeshHalfEdges, isotherms, mesh_half_edges, mesh_half_edges_workspace_bytes,  # noqa: F401
                        mesh_isolines, mesh_isolines_into, mesh_isolines_workspace_bytes, mesh_sections)
 from .mesh import (MeshExporter, ThermalMesh, camera_pose, grid_dims, mesh_extract, mesh_params, mesh_scan_width,  # noqa: F401
