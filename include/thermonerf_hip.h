@@ -1537,6 +1537,87 @@ int tn_mesh_spots(const float *positions, const float *temperature, const int32_
                   int32_t *vertex_spot, int32_t *face_spot, tn_mesh_spot *spots, int64_t *counts, void *workspace,
                   size_t workspace_bytes, void *stream);
 
+/* Geodesic distance on an indexed triangle list: the distance ALONG THE SURFACE from a set of seeds to every vertex, and the decay
+ * profile — area and temperature per band of that distance.  positions [V, 3] floats, triangles [T, 3] int32; offsets / corners are
+ * tn_mesh_incidence's of the SAME triangles and V.  The solver is a Jacobi fixed point of the eikonal equation on the triangles with
+ * the "virtual source" update: first order, exact on a plane from a point, no unfolding of obtuse triangles.  Every output is defined
+ * to the bit: all arithmetic is fp64 from the fp32 positions, one rounded operation per named step (add, sub, mul, div, sqrt:
+ * __dadd_rn ... __dsqrt_rn), no contraction; dot(x, y) = add(add(mul(x0, y0), mul(x1, y1)), mul(x2, y2)), norm(x) = sqrt(dot(x, x)).
+ *   STATE       distance (fp64 [V]) and nearest_seed (int32 [V]): D and L below; counts (device int64 [2], KEPT between calls): [0] the
+ *               rounds that changed a vertex, [1] 1 once a round has changed nothing.
+ *   RESTART     (restart != 0) counts = 0; every D = +inf, L = -1; then for the seeds i = 0 .. num_seeds - 1 ascending, with
+ *               v = seed_vertex[i] and o = add(seed_offset[i], 0.0) (-0.0 is +0.0): where o < D[v], D[v] = o and L[v] = i.  A repeated
+ *               vertex so keeps its smallest offset and, among equal offsets, the lowest i.  A seed with v outside [0, V) or an offset
+ *               that is not finite or below zero is ignored.  (Two integer atomic minima: the offset's bit pattern, then i.)
+ *   ROUND       reads D_k, L_k only and writes D_k+1, L_k+1 only (two arrays of each; never in place).  For vertex c: best = D_k[c],
+ *               label = L_k[c].  If c's three coordinates are finite, the corners (t, j) of c's list in list order — the list clipped
+ *               to [0, 3T], a corner outside it skipped — with triangle t VALID (three indices in [0, V)), t[j] == c, the three indices
+ *               distinct and the coordinates of a = t[(j + 1) % 3] and b = t[(j + 2) % 3] finite give three candidates, in this order:
+ *                 ac = c - a, bc = c - b, ab = b - a (sub per coordinate)
+ *                 via a    add(D[a], norm(ac)), label L[a]
+ *                 via b    add(D[b], norm(bc)), label L[b]
+ *                 face     only with D[a] and D[b] finite, u = norm(ab) > 0 and cy > 0, where
+ *                          cr = ab x ac: cr0 = sub(mul(ab1, ac2), mul(ab2, ac1)), cr1 = sub(mul(ab2, ac0), mul(ab0, ac2)),
+ *                                        cr2 = sub(mul(ab0, ac1), mul(ab1, ac0))
+ *                          cx = div(dot(ab, ac), u), cy = div(norm(cr), u)
+ *                          A = mul(D[a], D[a]); sx = div(sub(add(mul(u, u), A), mul(D[b], D[b])), mul(2, u))
+ *                          sy2 = sub(A, mul(sx, sx)), which must be >= 0; sy = sqrt(sy2)
+ *                          dx = sub(cx, sx), h = add(cy, sy); xs = add(sx, div(mul(dx, sy), h)), which must lie in 0 < xs < u
+ *                          the candidate is sqrt(add(mul(dx, dx), mul(h, h))), its label L[a] if D[a] <= D[b], else L[b]
+ *               A candidate replaces best and label iff cand < best and cand <= max_distance: ties keep the earlier candidate, a NaN
+ *               never wins.  D_k+1[c] = best, L_k+1[c] = label.  A value only ever decreases; a round that changes no vertex ends the
+ *               solve.  The number of rounds is about the number of edge hops to the farthest vertex.
+ * tn_mesh_geodesic queues, on `stream`, the restart (if asked) and `rounds` rounds (0 .. 4096).  Once a round has changed nothing the
+ * remaining queued rounds return on a device flag, as tn_mesh_register's iterations do.  After the call distance / nearest_seed hold
+ * the latest iterate whatever the parity (a last launch copies it from the workspace if the number of rounds that changed something
+ * in this call is odd).  restart == 0 continues the solve of the last call: the SAME distance, nearest_seed, counts and workspace,
+ * unchanged in between.  Every vertex is evaluated in every round.
+ * workspace: tn_mesh_geodesic_workspace_bytes(V, T) device bytes, 8-byte aligned; 0 for counts out of range.  V == 0: TN_OK, nothing is
+ * launched or written.  T == 0: the seeds keep their offsets, the first round changes nothing.
+ * Errors, all before any launch, in this order: tn_mesh_smooth's set for an indexed mesh (TN_ERR_NULL: with V > 0 positions, offsets
+ * or distance, with V > 0 and T > 0 triangles or corners; TN_ERR_SHAPE: V or T out of range, a pointer not 4-byte aligned); TN_ERR_NULL:
+ * with V > 0 nearest_seed, counts or the workspace; with V > 0, restart != 0 and num_seeds > 0 seed_vertex or seed_offset; TN_ERR_SHAPE:
+ * num_seeds < 0 or > 2^31 - 1, max_distance negative or a NaN (+inf: no limit), rounds < 0 or > 4096, distance / seed_offset / counts /
+ * workspace not 8-byte aligned, nearest_seed / seed_vertex not 4-byte aligned; TN_ERR_WORKSPACE: workspace_bytes too small (with V > 0).
+ *
+ * tn_mesh_distance_bands: the decay profile of `temperature` (floats [V]) over `distance`.  width (fp64, finite, > 0), bands = K in
+ * 1 .. 4096, cell: -1 for every face, otherwise only faces whose three vertices have nearest_seed == cell.  Face t TAKES PART iff it is
+ * PLACED as tn_mesh_regions defines it (indices distinct and in [0, V), nine finite coordinates), its three distances d0, d1, d2 are
+ * finite, the cell admits it, and q = div(div(add(add(d0, d1), d2), 3), width) satisfies 0 <= q < K; its band is floor(q).
+ *   tn_mesh_band, row k of `rows` (40 bytes, no padding, K rows, all written): area = SUM2 of the areas of the band's faces;
+ *               warm_area = SUM2 of the areas of its faces that have a face temperature tf (three finite temperatures; a face
+ *               without one enters these two sums as +0.0); mean_temperature = (float)div(SUM2 of mul(area, (double)tf), warm_area),
+ *               the NaN 0x7fc00000 unless warm_area > 0; min_temperature / max_temperature of tf, that NaN without a warm face;
+ *               faces, warm_faces; reserved = 0.  area, tf and SUM2 — the stable device sort of (band, face), the records joined in
+ *               ascending face index, 256 at a time, then the partials in block order — are tn_mesh_regions'.  An empty band is a
+ *               row of zeros with that NaN in its three floats.
+ *   counts (device int64 [3], OVERWRITTEN): [0] the bands that have a face, [1] the faces that take part, [2] the placed faces with
+ *               three finite distances that the cell admits (those beyond the last band included).
+ * workspace: tn_mesh_distance_bands_workspace_bytes(V, T, K) device bytes, 8-byte aligned; 0 for counts or K out of range.  V == 0 or
+ * T == 0: the rows are all empty.  TN_ERR_NULL: rows, counts or the workspace; with V > 0 positions, temperature, distance or
+ * nearest_seed; with T > 0 triangles; TN_ERR_SHAPE: V or T out of range, K < 1 or > 4096, width not finite or not > 0, cell < -1, a
+ * float / int32 pointer not 4-byte aligned, distance / rows / counts / workspace not 8-byte aligned; TN_ERR_WORKSPACE.  All before any
+ * launch, in the order of the code: rows / counts / workspace, the shape, the other pointers, the alignment, the workspace.
+ * Both entries launch plain 256-thread blocks (the scans: one block of 1024) on `stream` only: no allocation, no host synchronisation,
+ * no float atomics (the integer ones: the seeds', the tally's, the sort's), no block waits for another.  The kernels check what they
+ * dereference.  Inputs and outputs must not overlap. */
+typedef struct tn_mesh_band {
+    double area, warm_area;
+    float mean_temperature;
+    float min_temperature, max_temperature;
+    int32_t faces, warm_faces;
+    int32_t reserved;
+} tn_mesh_band;
+size_t tn_mesh_geodesic_workspace_bytes(int64_t num_vertices, int64_t num_triangles);
+int tn_mesh_geodesic(const float *positions, const int32_t *triangles, int64_t num_triangles, int64_t num_vertices,
+                     const int32_t *offsets, const int32_t *corners, const int32_t *seed_vertex, const double *seed_offset,
+                     int64_t num_seeds, double max_distance, int32_t restart, int32_t rounds, double *distance,
+                     int32_t *nearest_seed, int64_t *counts, void *workspace, size_t workspace_bytes, void *stream);
+size_t tn_mesh_distance_bands_workspace_bytes(int64_t num_vertices, int64_t num_triangles, int64_t bands);
+int tn_mesh_distance_bands(const float *positions, const float *temperature, const int32_t *triangles, int64_t num_vertices,
+                           int64_t num_triangles, const double *distance, const int32_t *nearest_seed, double width, int64_t bands,
+                           int32_t cell, tn_mesh_band *rows, int64_t *counts, void *workspace, size_t workspace_bytes, void *stream);
+
 /* ------------------------------------------------------------------------------------------------------
  * Fused forward: Model.forward (collider) + ThermalNerfModel.get_outputs
  * [REF thermal_nerf_model.py:210-275]

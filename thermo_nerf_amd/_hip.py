@@ -345,6 +345,10 @@ SIGNATURES = {
     "tn_mesh_spots_workspace_bytes": (_sz, [_i64, _i64, _i64]),
     "tn_mesh_spots": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp,
                                 _sz, _vp]),
+    "tn_mesh_geodesic_workspace_bytes": (_sz, [_i64, _i64]),
+    "tn_mesh_geodesic": (C.c_int, [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _i64, C.c_double, _i32, _i32, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "tn_mesh_distance_bands_workspace_bytes": (_sz, [_i64, _i64, _i64]),
+    "tn_mesh_distance_bands": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, C.c_double, _i64, _i32, _vp, _vp, _vp, _sz, _vp]),
     "tn_render_workspace_bytes": (_sz, [C.POINTER(tn_render_config), _i64]),
     "tn_render_rays_fwd": (
         C.c_int,

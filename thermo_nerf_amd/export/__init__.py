@@ -21,11 +21,16 @@
   NaN-aware smoothing of the degrees that comes first, which also fills the holes where nothing was measured.
 - hotspots.py: the hot and cold spots of a mesh by topological persistence: every peak's prominence in degrees against its own
   surroundings, the extent of each spot that stands out and its area, mean temperature and location.
+- geodesic.py: the distance along the surface from a set of seeds (the tape measure, the buffer around a region, the equidistant
+  curves through the isotherms of the distance) and the decay profile: area and degrees per band of distance from a hot spot.
 - ply.py: their PLY files.  _common.py: the argument checks they share.  cli.py: what the command lines under tools/ share.
 """
 from .closest import ClosestPoints, MeshDifference, mesh_closest, mesh_closest_into, mesh_difference  # noqa: F401
 from .components import (ComponentsInfo, MeshComponents, filter_components, mesh_components,  # noqa: F401
                          mesh_components_workspace_bytes, remove_small_components)
+from .geodesic import (BAND_BYTES, BAND_DTYPE, DistanceProfile, MeshDistance, distance_at_points, distance_profile,  # noqa: F401
+                       geodesic_distance, mesh_distance_bands_workspace_bytes, mesh_geodesic_workspace_bytes, seeds_at_points,
+                       seeds_of_regions, surface_distance)
 from .gradient import (MeshGradient, ScalarGradient, fill_temperature, mesh_scalar_gradient_workspace_bytes,  # noqa: F401
                        scalar_gradient, smooth_temperature, smooth_values, thermal_gradient)
 from .hotspots import (SADDLE_DTYPE, SPOT_BYTES, SPOT_DTYPE, BasinPersistence, MeshPeaks, ThermalHotspots,  # noqa: F401

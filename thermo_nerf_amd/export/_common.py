@@ -73,6 +73,16 @@ def mesh_arrays(mesh, temperature: bool = True) -> Tuple[Tensor, Optional[Tensor
     return p, t, tri, int(v), int(tri.shape[0])
 
 
+def check_incidence(incidence, tri: Tensor, v: int, t: int):
+    """a caller's ``MeshIncidence`` for an entry that walks its lists: int32 device tensors of V + 1 offsets and 3 T corners on the
+    triangles' device"""
+    offsets = _hip.require_device_tensor(incidence.offsets, "offsets", torch.int32)
+    corners = _hip.require_device_tensor(incidence.corners, "corners", torch.int32)
+    if offsets.numel() != v + 1 or corners.numel() != 3 * t or offsets.device != tri.device or corners.device != tri.device:
+        raise ValueError("incidence does not belong to a mesh of these vertices and triangles")
+    return incidence
+
+
 def color_array(colors, name: str, v: int, dev) -> Tensor:
     """a mesh's ``colors`` or ``thermal_colors`` for an entry that reads them: uint8 [V, 3]; one placeholder row for a mesh without
     vertices, whose colours nothing reads (an empty tensor has no address)"""

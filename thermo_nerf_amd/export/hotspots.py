@@ -24,7 +24,7 @@ import torch
 from torch import Tensor
 
 from .. import _hip
-from ._common import mesh_arrays, require_triangles, workspace_of
+from ._common import check_incidence, mesh_arrays, require_triangles, workspace_of
 from .gradient import smooth_temperature
 from .mesh import ThermalMesh
 from .smooth import MeshIncidence, mesh_incidence
@@ -120,16 +120,6 @@ def mesh_spots_workspace_bytes(num_vertices: int, num_triangles: int, num_spots:
     return int(_hip.load().tn_mesh_spots_workspace_bytes(int(num_vertices), int(num_triangles), int(num_spots)))
 
 
-def _incidence(incidence: Optional[MeshIncidence], tri: Tensor, v: int, t: int) -> MeshIncidence:
-    if incidence is None:
-        return mesh_incidence(tri, v)
-    offsets = _hip.require_device_tensor(incidence.offsets, "offsets", torch.int32)
-    corners = _hip.require_device_tensor(incidence.corners, "corners", torch.int32)
-    if offsets.numel() != v + 1 or corners.numel() != 3 * t or offsets.device != tri.device or corners.device != tri.device:
-        raise ValueError("incidence does not belong to a mesh of these vertices and triangles")
-    return incidence
-
-
 @torch.no_grad()
 def mesh_peaks(mesh: ThermalMesh, incidence: Optional[MeshIncidence] = None, coldest: bool = False,
                workspace: Optional[Tensor] = None) -> MeshPeaks:
@@ -139,7 +129,7 @@ def mesh_peaks(mesh: ThermalMesh, incidence: Optional[MeshIncidence] = None, col
     _, temp, tri, v, t = mesh_arrays(mesh)
     temp = temp.reshape(-1)
     dev = tri.device
-    inc = _incidence(incidence, tri, v, t)
+    inc = mesh_incidence(tri, v) if incidence is None else check_incidence(incidence, tri, v, t)
     workspace, size = workspace_of(workspace, mesh_peaks_workspace_bytes(v, t) if v else 0, dev)
     with torch.cuda.device(dev):
         rank = torch.empty((v,), dtype=torch.int32, device=dev)
